@@ -57,8 +57,8 @@ for _p in (ROOT, os.path.join(ROOT, "bench")):
 # Everything that is not the contract itself lives in bench/ (VERDICT r03 next-8): bench_measure.py = statistics, HIP-event
 # timing loops and the extra blocks of the N = 1 line; bench_single_process.py = `--gpus N` without a launcher.  This file
 # keeps the arguments, the CPU-baseline leg (the only code allowed to touch oracle/), the timed region and the JSON line.
-from bench_measure import (BYTES_PER_NT, HBM_PEAK_GBS, HOST_TIER_LOG2, crossover, device_row, first_contact_devices, gbs, gpu_numa_node,  # noqa: E402,F401
-                           host_placement, load_probes, measure_ceilings, measure_codec5, host_tier_block, measure_config3_64gib,
+from bench_measure import (BYTES_PER_NT, HBM_PEAK_GBS, HOST_TIER_LOG2, DUMP_WORDS, crossover, device_row, dump_outputs, first_contact_devices,  # noqa: E402,F401
+                           gbs, gpu_numa_node, host_placement, load_probes, measure_ceilings, measure_codec5, host_tier_block, measure_config3_64gib,
                            measure_configs_1gib, measure_host_tier, measure_packed_ops, measure_pcie, measure_traffic_live, numpy_pack,
                            physical_cores, require_free_hbm, sockets, stats_ms, timed_calls, timed_queued, traffic_for_line)
 
@@ -74,7 +74,13 @@ def parse_args():
     p.add_argument("--no-extras", action="store_true", help="headline only: skip the ceilings, the configs block and the fused pass")
     p.add_argument("--no-live-traffic", action="store_true", help="do not spawn the two rocprofv3 --pmc child runs; quote profiles/hbm_traffic.json")
     p.add_argument("--shard-log2-nt", type=int, default=35, help="per-GPU shard of BASELINE.json configs[4] (256 GiB over 8 GPUs = 2^35 nt each)")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", nargs="?", const=os.path.join(ROOT, "bench_outputs"),
+                   help="after the timed steps, write a seeded sample of what the last one computed to DIR/*.npy, 64 MB at most over "
+                        "all shards (bench/bench_measure.py dump_outputs); without DIR: bench_outputs/ in the repository, ignored by git")
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
 
 
 def cpu_baseline(seconds, faithful_tables=True):
@@ -364,6 +370,8 @@ def main():
     elapsed = time.perf_counter() - t0
 
     elapsed = allreduce([elapsed], dist.ReduceOp.MAX)[0]
+    if args.dump_outputs:  # before the verification and the extras below write these buffers again
+        dump_outputs(args.dump_outputs, torch, d_packed, d_out, n_len, args.seed, lo // 32, world, "" if world == 1 else "shard%d_" % rank)
     enc_list = [e[0].elapsed_time(e[1]) for e in ev]
     dec_list = [e[1].elapsed_time(e[2]) for e in ev]
     enc_ms, dec_ms = statistics.fmean(enc_list), statistics.fmean(dec_list)

@@ -20,6 +20,36 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec, /opt/skills/guides/MI355X_MICROARCH.
 BYTES_PER_NT = 1.25    # algorithmic bytes per nucleotide, each direction
 
 
+DUMP_WORDS = 1 << 18  # packed words --dump-outputs samples over ALL shards of a run: 2 + 4 + 32 MiB of .npy files
+
+
+def dump_outputs(out_dir, torch, d_packed, d_out, n_len, seed, first_word=0, shards=1, prefix=""):
+    """bench.py --dump-outputs: what the timed step hands its caller for one shard -- the packed words of the encode and the
+    ASCII of the decode -- as .npy files, so that two builds can be compared output for output on the same seeded input.
+    A fixed sample of DUMP_WORDS // shards words of the shard (all of them when there are fewer; its first and last word
+    always), chosen by `seed` and the shard's first global word `first_word`:
+      <prefix>words_index.npy  float64 [k]      global index w of each sampled word
+      <prefix>packed_words.npy float64 [k, 2]   word w as its low and high 32 bits (exact in float64)
+      <prefix>decoded.npy      float32 [k, 32]  decoded bytes 32 w .. 32 w + 31; -1 past the end of the shard"""
+    import numpy as np
+
+    words, k = d_packed.numel(), max(2, DUMP_WORDS // shards)
+    if words <= k:
+        idx = np.arange(words, dtype=np.int64)
+    else:
+        rng = np.random.default_rng([seed, first_word])
+        idx = np.union1d(rng.choice(words - 2, k - 2, replace=False) + 1, [0, words - 1]).astype(np.int64)
+    t_idx = torch.from_numpy(idx).to(d_packed.device)
+    packed = d_packed.index_select(0, t_idx).cpu().numpy().view(np.uint64)
+    pos = t_idx[:, None] * 32 + torch.arange(32, device=d_packed.device)
+    dec = d_out.index_select(0, pos.clamp(max=n_len - 1).reshape(-1)).reshape(-1, 32).cpu().numpy().astype(np.float32)
+    dec[(pos >= n_len).cpu().numpy()] = -1.0
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "words_index.npy"), (idx + first_word).astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "packed_words.npy"), np.stack([packed & 0xFFFFFFFF, packed >> 32], axis=1).astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "decoded.npy"), dec)
+
+
 def physical_cores(cpus):
     """distinct (package, core) pairs among the CPUs this process may run on"""
     seen = set()

@@ -21,7 +21,8 @@ import os
 import statistics
 import time
 
-from bench_measure import BYTES_PER_NT, HBM_PEAK_GBS, device_row, first_contact_devices, gbs, numpy_pack, require_free_hbm, stats_ms, traffic_for_line
+from bench_measure import (BYTES_PER_NT, HBM_PEAK_GBS, device_row, dump_outputs, first_contact_devices, gbs, numpy_pack, require_free_hbm, stats_ms,
+                           traffic_for_line)
 
 
 def main_single_process(args, cpu_baseline=None):
@@ -132,6 +133,9 @@ def main_single_process(args, cpu_baseline=None):
         run_steps(q, args.warmup, a_in, a_len, a_pk, a_words, a_out, N)  # queued while the generators may still be running
     sync_all()  # the timed region starts from idle devices (the contract's synchronize-on-both-sides), not for ordering
     elapsed, host_s, ms_e, ms_d = run_steps(q, args.steps, a_in, a_len, a_pk, a_words, a_out, N)  # the wait drains every device
+    if args.dump_outputs:  # before the shard-0-alone steps, the verification and the extras below write these buffers again
+        for k in range(N):
+            dump_outputs(args.dump_outputs, torch, d_pk[k], d_out[k], lens_l[k], args.seed, parts[k][0] // 32, N, "shard%d_" % k)
 
     # the same K steps for shard 0 alone, through a one-shard queue: what one device costs without the fan-out
     q1 = open_queue(1)

@@ -210,3 +210,37 @@ def test_the_pmc_child_of_an_n_gpu_line_sees_one_device():
     assert bm.one_device_env({"CUDA_VISIBLE_DEVICES": "4,5", "HIP_VISIBLE_DEVICES": "2"}, 0) == dict(gone, ROCR_VISIBLE_DEVICES="2", HIP_VISIBLE_DEVICES="0")
     env = bm.apply_env({"CUDA_VISIBLE_DEVICES": "4,5", "PATH": "/bin"}, bm.one_device_env({"CUDA_VISIBLE_DEVICES": "4,5"}, 1))
     assert env == {"PATH": "/bin", "ROCR_VISIBLE_DEVICES": "5", "HIP_VISIBLE_DEVICES": "0"}
+
+
+@pytest.mark.parametrize("n_len, shards, first_word", [(32 * 1000 + 13, 1, 0), (32 * ((1 << 18) + 4096), 1, 0), (32 * (1 << 17) + 5, 3, 1 << 20)])
+def test_dump_outputs_writes_the_callers_arrays(oracle, tmp_path, n_len, shards, first_word):
+    """--dump-outputs on CPU tensors: every word when there are few, a fixed seeded sample of 2^18 / shards words (first and
+    last included) when there are more; the files restate the packed words exactly and the decoded bytes, -1 past the end,
+    under their global word indices; N shards of a run stay within the 64 MB budget together; the same seed writes the same
+    files."""
+    import torch
+
+    import bench
+
+    n = oracle.fill_random_acgt(n_len, 9)
+    words = oracle.n_to_bits_lut(n)
+    d_packed, d_out = torch.from_numpy(words.view(np.int64).copy()), torch.from_numpy(n.copy())
+    prefix = "" if shards == 1 else "shard1_"
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), torch, d_packed, d_out, n_len, 0x5EED, first_word, shards, prefix)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == [prefix + f for f in ("decoded.npy", "packed_words.npy", "words_index.npy")]
+    assert shards * sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    idx = np.load(tmp_path / "a" / (prefix + "words_index.npy"))
+    pk = np.load(tmp_path / "a" / (prefix + "packed_words.npy"))
+    dec = np.load(tmp_path / "a" / (prefix + "decoded.npy"))
+    assert idx.dtype == pk.dtype == np.float64 and dec.dtype == np.float32
+    k = min(words.size, bench.DUMP_WORDS // shards)
+    assert idx.shape == (k,) and pk.shape == (k, 2) and dec.shape == (k, 32)
+    w = idx.astype(np.int64) - first_word
+    assert w[0] == 0 and w[-1] == words.size - 1 and np.all(np.diff(w) > 0)
+    assert np.array_equal(pk[:, 0].astype(np.uint64) | (pk[:, 1].astype(np.uint64) << np.uint64(32)), words[w])
+    pos = w[:, None] * 32 + np.arange(32)
+    assert np.array_equal(dec, np.where(pos < n_len, n[np.minimum(pos, n_len - 1)].astype(np.float32), np.float32(-1)))

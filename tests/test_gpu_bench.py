@@ -76,23 +76,54 @@ def test_single_gpu_line_small():
     assert abs(j["value"] - j["config"]["nt_per_step"] * j["steps"] / (j["ms_per_step"] * 1e-3 * j["steps"]) / 1e9) < 0.01 * j["value"]
 
 
+def _check_dump(d, shards, shard_nt, oracle):
+    """the files bench.py --dump-outputs wrote to `d`: one set per shard (prefixed shard<k>_ when there are several), 64 MB at
+    most in all, each shard's first and last word among its samples, and every sampled word and its 32 decoded bytes equal
+    to the oracle's on the run's seeded input (`shards` contiguous shards of `shard_nt` nt)"""
+    import numpy as np
+
+    prefixes = [""] if shards == 1 else ["shard%d_" % k for k in range(shards)]
+    files = sorted(os.listdir(d))
+    assert files == sorted(p + f for p in prefixes for f in ("decoded.npy", "packed_words.npy", "words_index.npy")), files
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in files) <= 64 << 20
+    n = oracle.fill_random_acgt(shards * shard_nt, 0x5EED)
+    for k, p in enumerate(prefixes):
+        w = np.load(os.path.join(d, p + "words_index.npy")).astype(np.int64)
+        assert w[0] == k * shard_nt // 32 and w[-1] == (k + 1) * shard_nt // 32 - 1 and np.all(np.diff(w) > 0)
+        text = n[w[:, None] * 32 + np.arange(32)]
+        pk = np.load(os.path.join(d, p + "packed_words.npy"))
+        assert np.array_equal(pk[:, 0].astype(np.uint64) | (pk[:, 1].astype(np.uint64) << np.uint64(32)), oracle.n_to_bits_lut(text.reshape(-1))), p
+        assert np.array_equal(np.load(os.path.join(d, p + "decoded.npy")), text.astype(np.float32)), p
+
+
+def test_dump_outputs_are_the_timed_steps_results(oracle, tmp_path):
+    """bench.py --dump-outputs: the packed words and decoded ASCII of the last timed step, sampled, equal the oracle's on the
+    seeded input the run generated on the device; --steps sets the number of timed steps."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "1", "--log2-nt", "24", "--no-extras",
+                          "--cpu-seconds", "0", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = _last_json(out.stdout)
+    assert j["steps"] == 4 and j["ms_per_step"] > 0 and j["verified"] is True
+    _check_dump(tmp_path, 1, 1 << 24, oracle)
+    import numpy as np
+
+    assert len(np.load(tmp_path / "words_index.npy")) == 1 << 18
+
+
 @pytest.mark.parametrize("n", [4, 8])
-def test_both_bench_forms_folded_onto_one_gpu(n):
-    """the two N > 1 forms of bench.py -- one rank per GPU under torch.distributed.run (the driver's) and
-    ONE process over N devices through the enqueue-only sharded tier -- with N = 4 and 8 shards folded onto this box's GPU:
-    same JSON contract, N rows, verified, and for the single-process form the fan-out's cost on the line
-    (`scaling_overhead_us`: wall per step over N shards minus N x the wall per step of shard 0 alone; <= 1 % of a 3.1-ms
-    kernel) with the host's enqueue time per step beside it."""
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        port = s.getsockname()[1]
+def test_single_process_form_folded_onto_one_gpu(n, oracle, tmp_path):
+    """ONE process over N devices through the enqueue-only sharded tier, with N = 4 and 8 shards folded onto
+    this box's GPU: same JSON contract, N rows, verified, the fan-out's cost on the line (`scaling_overhead_us`: wall per step
+    over N shards minus N x the wall per step of shard 0 alone; <= 1 % of a 3.1-ms kernel) with the host's enqueue time per
+    step beside it, and --dump-outputs: one sample per shard, all of them within the budget, equal to the oracle's words.
+    The other N > 1 form, one rank per GPU, is test_rank_form_folded_onto_one_gpu."""
     env = dict(os.environ, CNT_BENCH_SHARE_GPU="1")
-    # VERDICT r04 next-1: every N > 1 line is a full contract line -- `cpu_baseline` (the CPU leg runs in one of the two forms per
-    # N here, 1 s of it: the single-process form at N = 4, the rank form at N = 8) and a non-null, labelled `roofline.traffic`
-    cpu_single, cpu_ranks = ("1", "0") if n == 4 else ("0", "1")
-    common = ["--gpus", str(n), "--steps", "20", "--warmup", "2", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_ranks]
-    # (a) one process, N shards, everything queued, one wait (100 steps: the overhead figure multiplies a one-shard wall time by N)
-    single = ["--gpus", str(n), "--steps", "100", "--warmup", "5", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_single]
+    # VERDICT r04 next-1: every N > 1 line is a full contract line -- `cpu_baseline` (1 s of the CPU leg at N = 4 here, none at
+    # N = 8) and a non-null, labelled `roofline.traffic`
+    cpu_single = "1" if n == 4 else "0"
+    # one process, N shards, everything queued, one wait (100 steps: the overhead figure multiplies a one-shard wall time by N)
+    single = ["--gpus", str(n), "--steps", "100", "--warmup", "5", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_single,
+              "--dump-outputs", str(tmp_path)]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + single, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     j = _last_json(out.stdout)
@@ -112,18 +143,37 @@ def test_both_bench_forms_folded_onto_one_gpu(n):
     assert all(r["encode_ms"]["n"] == 100 and r["encode_ms"]["p90"] >= r["encode_ms"]["p10"] > 0 for r in j["ranks"])
     assert [r["first_nt"] for r in j["ranks"]] == [k << 26 for k in range(n)]
     assert abs(j["value"] - j["config"]["nt_per_step"] * j["steps"] / (j["ms_per_step"] * 1e-3 * j["steps"]) / 1e9) < 0.01 * j["value"]
-    # (b) the driver's form: N ranks (sharing cuda:0 over gloo here), barrier + max over ranks
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
+    _check_dump(tmp_path, n, 1 << 26, oracle)
+
+
+@pytest.mark.parametrize("cpu_leg", [False, True])
+def test_rank_form_folded_onto_one_gpu(cpu_leg, oracle, tmp_path):
+    """the driver's N > 1 form -- one rank per GPU under torch.distributed.run -- with its ranks folded onto
+    this box's GPU over gloo: same JSON contract, one row per rank, verified, with and without the CPU leg, and --dump-outputs
+    from every rank into one directory: one sample per shard, within the budget together, equal to the oracle's words.  Three
+    ranks: every rank is a process with the GPU open, and beside them this test's process, the launcher and rank 0's
+    counter-collection child have it open too -- 4 ranks put 7 processes on the one shared device, more than the 6 it
+    allows.  N = 4 and 8 shards run in test_single_process_form_folded_onto_one_gpu."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    env = dict(os.environ, CNT_BENCH_SHARE_GPU="1")
+    ranks, cpu_ranks = 3, "1" if cpu_leg else "0"
+    common = ["--gpus", str(ranks), "--steps", "20", "--warmup", "2", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_ranks,
+              "--dump-outputs", str(tmp_path)]
+    # `ranks` ranks sharing cuda:0 over gloo, barrier + max over ranks
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py")] + common
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     j = _last_json(out.stdout)
-    assert j["n_gpus"] == n and j["verified"] is True and [r["rank"] for r in j["ranks"]] == list(range(n))
-    assert len({r["pid"] for r in j["ranks"]}) == n and j["devices"]["control_plane"] == "gloo"
-    assert j["config"]["nt_per_step"] == 2 * n * (1 << 26) and j["configs4_sharded_encode"]["ranks_measured"] == n
-    _full_contract_line(j, n, cpu_ranks == "1")
-    assert j["devices"]["distinct"] == 1 and j["devices"]["expected_distinct"] == n and j["devices"]["shared_gpu_test_hook"] is True
+    assert j["n_gpus"] == ranks and j["verified"] is True and [r["rank"] for r in j["ranks"]] == list(range(ranks))
+    assert len({r["pid"] for r in j["ranks"]}) == ranks and j["devices"]["control_plane"] == "gloo"
+    assert j["config"]["nt_per_step"] == 2 * ranks * (1 << 26) and j["configs4_sharded_encode"]["ranks_measured"] == ranks
+    _full_contract_line(j, ranks, cpu_ranks == "1")
+    assert j["devices"]["distinct"] == 1 and j["devices"]["expected_distinct"] == ranks and j["devices"]["shared_gpu_test_hook"] is True
     assert all(r["chip"]["compute_units"] > 0 and r["hbm_before"]["free_GiB"] > 1 for r in j["ranks"])
+    _check_dump(tmp_path, ranks, 1 << 26, oracle)
 
 
 def _full_contract_line(j, n, with_cpu):
