@@ -261,3 +261,109 @@ def np_bits_to_n_lut(bits, length):
     i = np.arange(length, dtype=np.uint64)
     codes = (bits[(i >> np.uint64(5)).astype(np.int64)] >> ((i & np.uint64(31)) << np.uint64(1))) & np.uint64(3)
     return _NP_BITS_LUT[codes.astype(np.int64)]
+
+
+# ---- whole-stream expected values (large-size checks) ------------------------------
+# The oracle's answer for a whole seeded stream of any length, computed chunk by chunk on a thread pool (the ctypes calls
+# release the GIL), so that a device output of 2^36 nt can be compared in full through one position-salted checksum.
+# Every function regenerates the stream the device generator writes into a buffer filled with `first_nt`:
+# fill_random_acgt for "encode" / "complement" / "reverse_complement" / hamming / validate, fill_random_acgtn for
+# "encode5".  `plants` are (index into that buffer, byte) pairs written into the regenerated ASCII before it is
+# encoded or validated, as a test writes them on the device (an array of shape (k, 2) is accepted too).
+STREAM_KINDS = ("encode", "encode5", "complement", "reverse_complement")
+STREAM_CHUNK_NT = 16 << 20  # 16 Mi nt: a few GiB of host memory at 64 workers
+
+
+def _workers(workers):
+    return workers or min(os.cpu_count() or 1, 64)
+
+
+def _plants(plants):
+    p = np.asarray(plants, dtype=np.int64).reshape(-1, 2)
+    order = np.argsort(p[:, 0], kind="stable")  # a later plant at the same position wins, as a later device write would
+    return p[order, 0].copy(), p[order, 1].astype(np.uint8)
+
+
+def _stream_ascii(five, seed, first_nt, lo, m, plants):
+    """bytes [lo, lo + m) of the buffer filled with (seed, first_nt), plants applied; any lo, generated from the word
+    boundary at or below first_nt + lo (the generators are only regenerable there) and sliced"""
+    g = first_nt + lo
+    g0 = g - g % 27 if five else g & ~31
+    n = (fill_random_acgtn if five else fill_random_acgt)(m + g - g0, seed, first_nt=g0)[g - g0 :]
+    pos, byt = plants
+    i, j = np.searchsorted(pos, lo), np.searchsorted(pos, lo + m)
+    if j > i:
+        n[pos[i:j] - lo] = byt[i:j]
+    return n
+
+
+def _chunks(n_len, chunk_nt, grain):
+    k = chunk_nt or STREAM_CHUNK_NT
+    k -= k % grain
+    if k <= 0:
+        raise ValueError("chunk_nt must hold at least one output word (%d nt)" % grain)
+    return [(lo, min(k, n_len - lo)) for lo in range(0, n_len, k)]
+
+
+def _run(fn, chunks, workers):
+    from concurrent.futures import ThreadPoolExecutor
+
+    lib()  # load once, before the workers
+    with ThreadPoolExecutor(max_workers=_workers(workers)) as ex:
+        return list(ex.map(lambda c: fn(*c), chunks))
+
+
+def stream_checksum(kind, seed, n_len, first_nt=0, plants=(), per_chunk=False, chunk_nt=None, workers=None):
+    """checksum_words of the oracle's output words for the stream of n_len nt at `first_nt`, salted with the GLOBAL word
+    index (first word = first_nt / 32, or / 27 for "encode5"): the value devutil.checksum_words(out, first_word=...) has
+    to give.  "complement" / "reverse_complement" are of n_to_bits_lut of the stream, length n_len.  per_chunk=True
+    returns the list of per-chunk checksums instead (chunks of `chunk_nt`, rounded down to whole output words)."""
+    if kind not in STREAM_KINDS:
+        raise ValueError("kind must be one of %s" % (STREAM_KINDS,))
+    five = kind == "encode5"
+    grain = 27 if five else 32
+    if first_nt % grain:
+        raise ValueError("first_nt must start an output word (a multiple of %d)" % grain)
+    w0 = first_nt // grain
+    pl = _plants(plants)
+
+    def chunk(lo, m):
+        if kind == "reverse_complement":
+            # output nt [lo, lo + m) are the complements of input nt [n_len - lo - m, n_len - lo), reversed: the prefix of
+            # the reverse complement of the input from the word boundary at or below n_len - lo - m up to n_len - lo
+            a = n_len - lo - m
+            a0 = a & ~31
+            x = n_to_bits_lut(_stream_ascii(False, seed, first_nt, a0, n_len - lo - a0, pl))
+            out = reverse_complement(x, n_len - lo - a0)[: (m + 31) // 32]
+        else:
+            x = (n_to_bits2_lut if five else n_to_bits_lut)(_stream_ascii(five, seed, first_nt, lo, m, pl))
+            out = complement(x, m) if kind == "complement" else x
+        return checksum_words(out, first_word=w0 + lo // grain)
+
+    sums = _run(chunk, _chunks(n_len, chunk_nt, grain), workers)
+    return sums if per_chunk else sum(sums) % (1 << 64)
+
+
+def stream_hamming(seed_a, seed_b, n_len, first_nt_a=0, first_nt_b=0, per_chunk=False, chunk_nt=None, workers=None):
+    """hamming of n_to_bits_lut of two streams of n_len nt (fill_random_acgt at seed_a / first_nt_a and seed_b /
+    first_nt_b, both multiples of 32)"""
+    if first_nt_a % 32 or first_nt_b % 32:
+        raise ValueError("first_nt_a / first_nt_b must be multiples of 32")
+    none = _plants(())
+
+    def chunk(lo, m):
+        a = n_to_bits_lut(_stream_ascii(False, seed_a, first_nt_a, lo, m, none))
+        b = n_to_bits_lut(_stream_ascii(False, seed_b, first_nt_b, lo, m, none))
+        return hamming(a, b, m)
+
+    counts = _run(chunk, _chunks(n_len, chunk_nt, 32), workers)
+    return counts if per_chunk else sum(counts)
+
+
+def stream_validate(seed, n_len, first_nt=0, plants=(), allow_n=False, per_chunk=False, chunk_nt=None, workers=None):
+    """validate of the fill_random_acgt stream of n_len nt at first_nt (any nt: the buffer may start inside a word),
+    plants applied"""
+    pl = _plants(plants)
+    counts = _run(lambda lo, m: validate(_stream_ascii(False, seed, first_nt, lo, m, pl), allow_n=allow_n),
+                  _chunks(n_len, chunk_nt, 1), workers)
+    return counts if per_chunk else sum(counts)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import need_free_hbm
+from stream_checks import assert_mutation_seen, check_words
 
 pytestmark = pytest.mark.gpu
 
@@ -350,6 +351,12 @@ def test_metric_16gib_round_trip_and_checksum_of_checksums(cn, oracle, torch_cud
         assert oracle.checksum_words(want, first_word=c * chunk_w) == sums[c], c
         got = packed[c * chunk_w : (c + 1) * chunk_w].cpu().numpy().view(np.uint64)
         assert np.array_equal(got, want), c
+    # every word against the oracle (a tile map that moves tiles consistently passes the round trip and misses the samples)
+    want_all = check_words(packed, "encode", 0xC0FFEE, n_len, label="metric encode", record=fullsize)
+    assert want_all == total
+    c_m = n_chunks // 4 + 1
+    assert c_m not in (0, 1, n_chunks // 2 + 3, n_chunks - 1)
+    assert_mutation_seen(packed, c_m * chunk_w + 12345, want_all)
 
 
 # ---- BASELINE.json configs[3]: encode + decode over a 64 GiB buffer (144 GiB resident) ----------
@@ -383,6 +390,11 @@ def test_config_64gib_round_trip_multi_launch(cn, oracle, torch_cuda, fullsize):
         want = oracle.n_to_bits_lut(host_n)
         got = packed[c * chunk_w : (c + 1) * chunk_w].cpu().numpy().view(np.uint64)
         assert np.array_equal(got, want), c
+    # every word against the oracle, both launches of the split included
+    want_all = check_words(packed, "encode", 0xBEEF, n_len, label="configs[3] encode", record=fullsize)
+    c_m = n_chunks // 3 + 7
+    assert c_m not in picks
+    assert_mutation_seen(packed, c_m * chunk_w + 4321, want_all)
 
 
 # ---- any-alignment plan: head peel + funnel-shifted loads (hip/device_tier.inc encode_dev/decode_dev) ----
@@ -654,10 +666,16 @@ def test_fused_round_trip_config3_64gib(cn, oracle, torch_cuda, fullsize):
         assert np.array_equal(got, oracle.n_to_bits_lut(host_n)), c
     tail = oracle.fill_random_acgt(2048 * 3 + 77, 36, first_nt=1 << 36)  # the ragged end behind the fused tiles
     assert np.array_equal(bits[(1 << 36) // 32 :].cpu().numpy().view(np.uint64), oracle.n_to_bits_lut(tail))
+    # every word against the oracle, not only against the plain encoder (itself only sampled)
+    want_all = check_words(bits, "encode", 36, n_len, label="configs[3] fused", record=fullsize)
+    c_m = n_chunks // 2 + 5
+    assert c_m not in (0, n_chunks // 3, n_chunks - 1)
+    assert_mutation_seen(bits, c_m * chunk_w + 999, want_all)
     # the same 64 GiB through the ANY-ALIGNMENT kernel (round 4: round_trip_window, two launches at this size, head and end as
     # edge items of the second): input at byte phase 5, packed words at word phase 1, decoded output at byte phase 77 of
     # buffers that hold a few bytes more; same words as the aligned call above, decoded copy equal to the input
     want_sum = devutil.checksum_words(bits)
+    assert want_sum == want_all
     del bits
     torch.cuda.empty_cache()
     pad_in = torch.empty(n_len + 128, dtype=torch.uint8, device="cuda")
@@ -671,7 +689,9 @@ def test_fused_round_trip_config3_64gib(cn, oracle, torch_cuda, fullsize):
     v_bits, v_back = pad_bits[1 : 1 + (n_len + 31) // 32], pad_back[77 : 77 + n_len]
     _, ms2 = _timed_ms(torch, lambda: cn.round_trip_dev(v_in, out_bits=v_bits, out_n=v_back))
     fullsize(36, ms2, config="configs[3] fused, misaligned (in +5 B, words +8 B, out +77 B)", nt=n_len, gbs=round(2.25 * n_len / ms2 / 1e6, 1))
+    check_words(v_bits, "encode", 36, n_len, label="configs[3] fused, misaligned", want=want_all)  # same stream, same words
     assert devutil.checksum_words(v_bits) == want_sum
+    assert_mutation_seen(v_bits, c_m * chunk_w + 999, want_all)
     assert bool((pad_bits[:1] == -1).all()) and bool((pad_bits[1 + (n_len + 31) // 32 :] == -1).all())
     assert bool((pad_back[:77] == 0x2A).all()) and bool((pad_back[77 + n_len :] == 0x2A).all())
     for lo in (0, (1 << 35) - 12345, n_len - (1 << 28)):  # decoded copy == input on three 256-MiB windows (torch compares, any alignment)
@@ -1088,7 +1108,8 @@ def test_config4_rank_shard_at_its_global_offset(cn, oracle, torch_cuda, fullsiz
     chunk_w = chunk_nt // 32
     n_chunks = (hi - lo) // chunk_nt
     rng = np.random.default_rng(100 + k)
-    for c in sorted({0, n_chunks - 1, int(rng.integers(1, n_chunks - 1)), int(rng.integers(1, n_chunks - 1))}):
+    sampled = sorted({0, n_chunks - 1, int(rng.integers(1, n_chunks - 1)), int(rng.integers(1, n_chunks - 1))})
+    for c in sampled:
         host_n = oracle.fill_random_acgt(chunk_nt, seed, first_nt=lo + c * chunk_nt)  # GLOBAL offset
         assert np.array_equal(d[c * chunk_nt : c * chunk_nt + 4096].cpu().numpy(), host_n[:4096]), (k, c)  # the shard holds the global stream
         want = oracle.n_to_bits_lut(host_n)
@@ -1096,6 +1117,10 @@ def test_config4_rank_shard_at_its_global_offset(cn, oracle, torch_cuda, fullsiz
         assert np.array_equal(got, want), (k, c)
         first_word = lo // 32 + c * chunk_w  # global word index: the salt of the checksum
         assert devutil.checksum_words(bits[c * chunk_w : (c + 1) * chunk_w], first_word=first_word) == oracle.checksum_words(want, first_word=first_word), (k, c)
+    # every word of the shard against the oracle at the global offset
+    want_all = check_words(bits, "encode", seed, hi - lo, first_nt=lo, label="configs[4] rank %d" % k, record=fullsize)
+    c_m = next(c for c in range(n_chunks // 2, n_chunks) if c not in sampled)
+    assert_mutation_seen(bits, c_m * chunk_w + 77, want_all, first_word=lo // 32)
     back = torch.empty(hi - lo, dtype=torch.uint8, device="cuda")
     sharding.bits_to_n_sharded_dev([bits], [hi - lo], outs=[back])
     assert devutil.count_mismatch(d, back) == 0

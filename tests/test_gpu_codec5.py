@@ -3,6 +3,8 @@ the CPU oracle; bit-exact."""
 import numpy as np
 import pytest
 
+from stream_checks import assert_mutation_seen, check_words
+
 pytestmark = pytest.mark.gpu
 
 ALPHA = np.frombuffer(b"ACGTNacgtnUu", dtype=np.uint8)
@@ -207,7 +209,7 @@ def test_every_variant(cn, oracle, lab_build, key):
         devutil.set_tuning(key, old)
 
 
-def test_large_ragged_size_64bit_indexing(cn, oracle):
+def test_large_ragged_size_64bit_indexing(cn, oracle, fullsize):
     import torch
 
     from cute_nucleotides_amd import devutil
@@ -222,6 +224,32 @@ def test_large_ragged_size_64bit_indexing(cn, oracle):
     first_word = packed.numel() - tail_words
     host = oracle.fill_random_acgtn(n_len - 27 * first_word, 31, first_nt=27 * first_word)
     assert np.array_equal(packed[first_word:].cpu().numpy().view(np.uint64), oracle.n_to_bits2_lut(host))
+    # every word against the oracle (the round trip above then covers the decoder in full)
+    want_all = check_words(packed, "encode5", 31, n_len, label="encode5 7.2 Gi nt", record=fullsize)
+    assert_mutation_seen(packed, packed.numel() // 3 + 5, want_all)
+    # the validated encoder on the same buffer with bytes outside ACGTUNacgtun planted on the device: on both sides of
+    # 2^31 and 2^32 bytes, at both ends and spread over the rest; strict mode encodes them like n_to_bits2_lut
+    rng = np.random.default_rng(2718)
+    edges = [0, (1 << 31) - 1, 1 << 31, (1 << 31) + 1, (1 << 32) - 1, 1 << 32, (1 << 32) + 1, n_len - 1]
+    pos = np.unique(np.concatenate([rng.integers(0, n_len, 300), edges]))
+    bad = np.frombuffer(bytes([0, 0xFF, 0x80]) + b"X-*z0", dtype=np.uint8)[rng.integers(0, 8, pos.size)]
+    assert oracle.validate(bad, allow_n=True) == pos.size
+    d[torch.from_numpy(pos).cuda()] = torch.from_numpy(bad).cuda()
+    plants = np.stack([pos, bad.astype(np.int64)], axis=1)
+    words, acc = cn.n_to_bits2_checked_dev(d, out=packed, strict_lut=True)
+    assert int(acc.item()) == pos.size
+    want_p = check_words(words, "encode5", 31, n_len, plants=plants, label="checked encode5 7.2 Gi nt, %d plants" % pos.size,
+                         record=fullsize)
+    assert want_p != want_all
+    words_s, acc_s = cn.n_to_bits2_checked_dev(d, out=packed, strict_lut=True, spread=True)
+    assert int(acc_s.sum().item()) == pos.size
+    check_words(words_s, "encode5", 31, n_len, plants=plants, label="checked encode5, spread counters", want=want_p)
+    # the default flags: the same count; the oracle defines no words for bytes outside the alphabet except in strict mode,
+    # so the words are held to the strict call's everywhere but in the words that hold a plant
+    words_d, acc_d = cn.n_to_bits2_checked_dev(d)
+    assert int(acc_d.item()) == pos.size
+    differ = torch.nonzero(words_d != words_s).flatten().cpu().numpy()
+    assert np.isin(differ, pos // 27).all(), differ[~np.isin(differ, pos // 27)][:10]
 
 
 def test_caller_supplied_outputs_are_validated(cn):

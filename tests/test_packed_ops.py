@@ -2,6 +2,8 @@
 validation.  These are NOT in the reference (parity unpinned): the CPU part pins the oracle's
 scalar definitions against plain-Python/ASCII-level definitions, the GPU part compares the
 HIP kernels with the oracle bit for bit and checks algebraic properties at large sizes."""
+import time
+
 import numpy as np
 import pytest
 
@@ -187,6 +189,132 @@ def test_gpu_large_properties(oracle):
     assert bytes(head) == bytes(tail).translate(COMP)[::-1]
     # the reductions above took their scratch from the stream-ordered allocator; none fell back to the slow path
     assert devutil.get_tuning("reduce_fallbacks") == 0
+
+
+VALIDATE_RUN = 16 << 10  # bytes per run of validate's persistent waves (hip/packed_ops_kernels.hpp kValidateRunKiB)
+
+
+def _large_validate_plants(n_len, seed=4242):
+    """(positions, bytes) planted for validate into a page-aligned buffer of n_len bytes.  The runs of the buffer are
+    [16 Ki r, 16 Ki (r+1)); those of the buffer from its byte 1 on start at byte 4096.  Region r gets 1..64 plants in
+    [16 Ki r, 16 Ki r + 4096) and, drawn independently, 1..64 in [16 Ki r + 4096, 16 Ki (r+1)): every run of both grids
+    holds plants, and their number varies from run to run (a dropped run and one counted twice change the total unless
+    the two hold the same count).  A few more sit on run boundaries +-1, at the edges of the shifted head and on the last
+    byte.  The bytes mix N / n with bytes outside every alphabet."""
+    rng = np.random.default_rng(seed)
+    R = n_len // VALIDATE_RUN
+    base = np.arange(R, dtype=np.int64) * VALIDATE_RUN
+    k_lo, k_hi = rng.integers(1, 65, R), rng.integers(1, 65, R)
+    lo = np.repeat(base, k_lo) + rng.integers(0, 4096, int(k_lo.sum()))
+    hi = np.repeat(base, k_hi) + rng.integers(4096, VALIDATE_RUN, int(k_hi.sum()))
+    edges = np.concatenate([(b[:, None] + np.array([-1, 0, 1])).ravel() for b in (base[1::997], base[1::991] + 4096)] + [np.array([1, 4095, 4096, n_len - 1])])
+    pos = np.unique(np.concatenate([lo, hi, edges]))
+    pos = pos[(pos >= 0) & (pos < n_len)]
+    alphabet = np.frombuffer(b"NnX-" + bytes([0, 0x80, 0xFF]), dtype=np.uint8)
+    return pos, alphabet[rng.integers(0, alphabet.size, pos.size)]
+
+
+def test_large_validate_plant_layout_tells_runs_apart():
+    """the plants of test_gpu_large_ops_match_the_oracle_in_full, on the CPU: every run of both grids (the page-aligned
+    buffer and the same buffer from byte 1 on) holds plants in both modes' strict count, and two runs almost never hold
+    the same (strict, allow_n) pair of counts -- so dropping one run while counting another twice moves a total"""
+    n_len = (1 << 32) + 77
+    pos, bad = _large_validate_plants(n_len)
+    is_n = (bad == ord("N")) | (bad == ord("n"))
+    for origin in (0, 4096):
+        n_runs = (n_len - origin) // VALIDATE_RUN
+
+        def per_run(p):
+            r = (p[p >= origin] - origin) // VALIDATE_RUN
+            return np.bincount(r[r < n_runs], minlength=n_runs)
+
+        strict, allow = per_run(pos), per_run(pos[~is_n])
+        assert strict.min() >= 2, origin
+        _, same_strict = np.unique(strict, return_counts=True)
+        _, same_pair = np.unique(strict * 4096 + allow, return_counts=True)
+        p_strict = float(((same_strict / n_runs) ** 2).sum())  # chance that two random runs share the strict count
+        p_pair = float(((same_pair / n_runs) ** 2).sum())
+        assert p_strict < 0.02 and p_pair < 0.002, (origin, p_strict, p_pair)
+
+
+@gpu
+def test_gpu_large_ops_match_the_oracle_in_full(oracle, fullsize):
+    """2^32 + 77 nt, every output compared with the oracle's whole-stream value (the properties above cannot see a
+    mistake that is consistent with itself: a mirrored index that is its own inverse, a dropped reduction run counted
+    twice by another): complement and reverse complement by full-length checksum, hamming against a second stream,
+    validate with plants in every 16-KiB run of both run grids (input on the page, and one byte off it) whose number
+    differs from run to run, so that a dropped run and a run counted twice do not cancel, N and bytes outside every
+    alphabet mixed so the two modes differ.  Then the same off the 16-B grid: streams at different
+    phases (hamming_generic over everything), complement from word phase 1 (complement_generic), reverse complement
+    into word phase 1, validate of d[1:] (head peel, runs at a shifted base).  Each check is shown to see one changed
+    word or byte that nothing sampled covers."""
+    import torch
+
+    import cute_nucleotides_amd as cn
+    from cute_nucleotides_amd import devutil, packed_ops as po
+    from stream_checks import assert_mutation_seen, check_hamming, check_validate, check_words
+
+    n_len = (1 << 32) + 77
+    W = (n_len + 31) // 32
+    buf = torch.empty(n_len + 4096, dtype=torch.uint8, device="cuda")
+    d = buf[(-buf.data_ptr()) % 4096 :][:n_len]  # on a page: validate's runs of d and of d[1:] then lie on different grids
+    devutil.fill_random_acgt(d, 6)
+    y = cn.n_to_bits_dev(d)
+    devutil.fill_random_acgt(d, 5)
+    x = cn.n_to_bits_dev(d)
+    c = po.complement_dev(x, n_len)
+    want_c = check_words(c, "complement", 5, n_len, label="complement", record=fullsize)
+    assert_mutation_seen(c, W // 2 + 12345, want_c)
+    del c
+    rc = po.reverse_complement_dev(x, n_len)
+    want_rc = check_words(rc, "reverse_complement", 5, n_len, label="reverse complement", record=fullsize)
+    assert_mutation_seen(rc, W // 3 + 54321, want_rc)
+    del rc
+    want_h = check_hamming(x, y, n_len, 5, 6)
+    i_m = W // 5 + 777  # one word of y made equal to x's: distance of that word drops to 0
+    saved = y[i_m : i_m + 1].clone()
+    y[i_m : i_m + 1].copy_(x[i_m : i_m + 1])
+    assert int(po.hamming_dev(x, y, n_len).item()) != want_h
+    y[i_m : i_m + 1].copy_(saved)
+    assert int(po.hamming_dev(x, y, n_len).item()) == want_h
+
+    # off the 16-B grid: w whole words from word 1 of x (nt 32 on), against words 0.. of y
+    w = n_len // 32 - 1
+    check_hamming(x[1 : 1 + w], y[0:w], 32 * w, 5, 6, first_nt_a=32, first_nt_b=0, label="hamming at different phases")
+    del y
+    cg = po.complement_dev(x[1 : 1 + w], 32 * w, out=torch.empty(w, dtype=torch.int64, device="cuda"))
+    check_words(cg, "complement", 5, 32 * w, first_nt=32, label="complement from word phase 1", record=fullsize)
+    del cg
+    obuf = torch.full((W + 2,), -1, dtype=torch.int64, device="cuda")
+    po.reverse_complement_dev(x, n_len, out=obuf[1 : 1 + W])
+    assert int(obuf[0].item()) == -1 and int(obuf[W + 1].item()) == -1
+    check_words(obuf[1 : 1 + W], "reverse_complement", 5, n_len, label="reverse complement into word phase 1", want=want_rc)
+    del obuf, x
+
+    # validate: d is on a page, so its runs are [16 Ki r, 16 Ki (r+1)); d[1:] peels 4095 head bytes and runs from d's
+    # byte 4096 on.  Every run of both grids holds plants, and their counts differ from run to run (the layout is pinned on
+    # the CPU by test_large_validate_plant_layout_tells_runs_apart).
+    pos, bad = _large_validate_plants(n_len)
+    n_bad_n = int(((bad == ord("N")) | (bad == ord("n"))).sum())
+    assert 0 < n_bad_n < pos.size
+    d[torch.from_numpy(pos).cuda()] = torch.from_numpy(bad).cuda()
+    plants = np.stack([pos, bad.astype(np.int64)], axis=1)
+    t0 = time.perf_counter()
+    for allow in (False, True):
+        want_v = check_validate(d, 5, n_len, plants=plants, allow_n=allow)
+        assert want_v == pos.size - (n_bad_n if allow else 0)
+        # d[1:]: the buffer filled at nt 0, seen from nt 1; plants shift by one, the one at byte 0 (if any) drops out
+        sh = plants[plants[:, 0] >= 1] - np.array([1, 0])
+        check_validate(d[1:], 5, n_len - 1, first_nt=1, plants=sh, allow_n=allow, label="validate of d[1:]")
+    fullsize(32, (time.perf_counter() - t0) * 1e3, check="full-length oracle: validate, %d plants" % pos.size)
+    p_m = int((n_len // VALIDATE_RUN) // 3 * VALIDATE_RUN + 4000)
+    while pos[np.searchsorted(pos, p_m)] == p_m:  # a byte no plant took
+        p_m += 1
+    orig = int(d[p_m].item())
+    d[p_m] = ord("X")
+    assert int(po.validate_dev(d).item()) == pos.size + 1
+    d[p_m] = orig
+    assert int(po.validate_dev(d).item()) == pos.size
 
 
 @gpu
