@@ -22,6 +22,7 @@ CNT_TAIL_LUT = 0x4
 CNT_SPREAD_COUNT = 0x8  # the *_checked device entry points: the counter is CNT_COUNT_SLOTS u64, the count their sum
 CNT_COUNT_SLOTS = 2048
 CNT_QUEUE_TIMED = 0x1
+CNT_KMER_CANONICAL = 0x10
 
 _vp, _sz, _u64, _int, _uint = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint
 
@@ -106,6 +107,8 @@ SIGNATURES = {
     "cnt_complement": (_int, [_vp, _sz, _vp]),
     "cnt_reverse_complement": (_int, [_vp, _sz, _vp]),
     "cnt_validate": (_int, [_vp, _sz, _uint, ctypes.POINTER(_u64)]),
+    "cnt_kmers_dev": (_int, [_vp, _sz, _uint, _uint, _vp, _sz, _vp]),
+    "cnt_kmers": (_int, [_vp, _sz, _uint, _uint, _vp, _sz]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

@@ -1,5 +1,5 @@
 """Operations on 2-bit packed nucleotides without decoding: Hamming distance,
-complement, reverse complement, and alphabet validation of ASCII buffers.  The reference does
+complement, reverse complement, k-mer extraction (forward and canonical), and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -11,6 +11,7 @@ from ._lib import check, lib
 from .n_to_bits import _counter, _dev_guard, _enqueue, _out_words, _p, _u8, _u64
 
 CNT_ALLOW_N = 0x2
+CNT_KMER_CANONICAL = 0x10
 
 
 def _need(bits, length):
@@ -42,6 +43,27 @@ def reverse_complement_hip(bits, length):
     out = np.empty(lib().cnt_words_for(length), dtype=np.uint64)
     check(lib().cnt_reverse_complement(_p(bits), length, _p(out)))
     return out
+
+
+def _n_kmers(length, k):
+    if not 1 <= k <= 32:
+        raise ValueError("k must be in 1..32")
+    return length - k + 1 if length >= k else 0
+
+
+def kmers_hip(bits, length, k, canonical=False, out=None):
+    """The length-k+1 k-mers of the sequence as np.uint64 (include/cute_nt.h "k-mers"): k-mer i packed like a sequence of
+    length k, or with canonical=True the smaller of it and its reverse complement as u64.  `out` (optional, >= m uint64, e.g.
+    from pinned_empty) receives them; the [:m] view is returned."""
+    bits = _u64(bits)
+    _need(bits, length)
+    m = _n_kmers(length, k)
+    if out is None:
+        out = np.empty(m, dtype=np.uint64)
+    elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size < m:
+        raise ValueError("out must be a contiguous uint64 array with >= %d elements" % m)
+    check(lib().cnt_kmers(_p(bits), length, k, CNT_KMER_CANONICAL if canonical else 0, _p(out), out.size))
+    return out[:m]
 
 
 def validate_hip(n, allow_n=False):
@@ -85,6 +107,21 @@ def complement_dev(bits, length, out=None):
 
 def reverse_complement_dev(bits, length, out=None):
     return _unary_dev(lib().cnt_reverse_complement_dev, bits, length, out)
+
+
+def kmers_dev(bits, length, k, canonical=False, out=None):
+    """Device tier of kmers_hip: `bits` an int64 CUDA tensor, the result the [:m] view of an int64 tensor (`out` if given)
+    enqueued on torch's current stream."""
+    torch = _dev_guard(bits)
+    if bits.dtype != torch.int64:
+        raise TypeError("packed words must be an int64 tensor")
+    if length > bits.numel() * 32:
+        raise ValueError("The length is greater than the number of nucleotides!")
+    m = _n_kmers(length, k)
+    out = _out_words(torch, out, m, bits)
+    _enqueue(bits, lib().cnt_kmers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
+             ctypes.c_void_p(out.data_ptr()), out.numel())
+    return out[:m]
 
 
 def validate_dev(n, allow_n=False, acc=None):

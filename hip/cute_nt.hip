@@ -782,3 +782,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 }  // extern "C"
 
 #include "packed_ops_abi.inc"
+#include "kmer_abi.inc"

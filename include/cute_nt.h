@@ -364,6 +364,19 @@ int cnt_complement(const uint64_t *bits, size_t len, uint64_t *out);
 int cnt_reverse_complement(const uint64_t *bits, size_t len, uint64_t *out);
 int cnt_validate(const uint8_t *n, size_t n_len, unsigned flags, uint64_t *invalid);
 
+/* k-mers, 1 <= k <= 32: the m = len-k+1 windows of k consecutive codes (len < k: none, CNT_OK without touching the device).
+ *   forward             out[i] = sum_{j<k} code(i+j) << 2j, i < m: the k-mer packed exactly like a sequence of length k
+ *                       (bits_to_n of [out[i]] with length k is bases i..i+k-1), bits 2k..63 zero
+ *   CNT_KMER_CANONICAL  out[i] = min(fwd, rc) as unsigned 64-bit integers, rc = sum_{j<k} (code(i+k-1-j) ^ 2) << 2j the
+ *                       reverse complement packed the same way.  The order is numeric order of this LSB-first packing, not
+ *                       lexicographic order of the letters.  Canonical k-mer i of s == canonical k-mer m-1-i of revcomp(s).
+ * Input bits beyond len are ignored; out[m..out_cap) is not written.  Errors: k == 0, k > 32, an unknown flag, a NULL or
+ * not 8-B aligned pointer (when m > 0), out overlapping the input words: CNT_EINVAL; out_cap < m: CNT_ECAP.  Device tier:
+ * enqueue-only like the ops above, pointers at any 8-B phase.  Host tier: synchronous, pinned in + out used in place. */
+#define CNT_KMER_CANONICAL 0x10u
+int cnt_kmers_dev(const void *d_bits, size_t len, unsigned k, unsigned flags, void *d_out, size_t out_cap, void *stream);
+int cnt_kmers(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *out, size_t out_cap);
+
 /* ---- device utilities for benches and large-size verification ----------------- */
 /* Counter-based uniform {A,C,G,T} (resp. {A,C,G,T,N}, P(N)=1/16) generator,
  * identical to oracle/cnt_oracle.c's, so a host can regenerate any chunk.

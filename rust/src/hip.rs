@@ -64,6 +64,8 @@ extern "C" {
     fn cnt_complement(bits: *const u64, len: usize, out: *mut u64) -> c_int;
     fn cnt_reverse_complement(bits: *const u64, len: usize, out: *mut u64) -> c_int;
     fn cnt_validate(n: *const u8, n_len: usize, flags: c_uint, invalid: *mut u64) -> c_int;
+    fn cnt_kmers_dev(d_bits: *const c_void, len: usize, k: c_uint, flags: c_uint, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
+    fn cnt_kmers(bits: *const u64, len: usize, k: c_uint, flags: c_uint, out: *mut u64, out_cap: usize) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -425,6 +427,25 @@ pub fn reverse_complement_hip(bits: &[u64], len: usize) -> Vec<u64> {
     res
 }
 
+const CNT_KMER_CANONICAL: c_uint = 0x10;
+
+/// The `len - k + 1` k-mers (`1 <= k <= 32`; none when `len < k`), each packed like a sequence of length `k`; with
+/// `canonical` the smaller of the k-mer and its reverse complement as `u64` (numeric order of the packing, not letter order).
+pub fn kmers_hip(bits: &[u64], len: usize, k: u32, canonical: bool) -> Vec<u64> {
+    need(bits, len);
+    if k == 0 || k > 32 {
+        panic!("k must be in 1..32");
+    }
+    let m = if len >= k as usize { len - k as usize + 1 } else { 0 };
+    let mut res: Vec<u64> = Vec::with_capacity(m);
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    unsafe {
+        check(cnt_kmers(bits.as_ptr(), len, k, flags, res.as_mut_ptr(), m));
+        res.set_len(m);
+    }
+    res
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -506,6 +527,15 @@ pub fn bits_to_n_hip_dev(d_bits: &DeviceBuffer, words: usize, len: usize, d_out:
     }
     assert!(words * 8 <= d_bits.bytes && len <= d_out.bytes);
     unsafe { check(cnt_bits_to_n_dev(d_bits.ptr, words, len, d_out.ptr, 0, std::ptr::null_mut())) };
+}
+
+/// Enqueue the `len - k + 1` k-mers of `len` device-resident nucleotides into `d_out` (>= that many words); see `kmers_hip`.
+pub fn kmers_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, canonical: bool, d_out: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    unsafe { check(cnt_kmers_dev(d_bits.ptr, len, k, flags, d_out.ptr, d_out.bytes / 8, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).

@@ -1,0 +1,379 @@
+"""k-mer extraction on packed words (include/cute_nt.h "k-mers"): forward and canonical k-mers, k = 1..32.  Not in the
+reference, so the CPU part pins a numpy reference against an ASCII-level definition (slice the letters, reverse-complement
+them with bytes.translate, pack each k-mer with the oracle), checks the ABI's argument errors and wiring, and the ISA of
+the new kernels; the GPU part compares both tiers with the numpy reference bit for bit, at every pointer phase, and checks
+the whole output of calls past 2^31 and 2^32 k-mers against a host checksum built chunk by chunk."""
+import ctypes
+import os
+import sys
+import time
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+COMP = bytes.maketrans(b"ACGT", b"TGCA")
+KS = [1, 2, 15, 16, 17, 31, 32]
+CPU_SIZES = [0, 1, "k-1", "k", 31, 32, 33, 63, 64, 65, 1000, 4099]
+CNT_KMER_CANONICAL = 0x10
+
+
+def _sizes(k, extra=()):
+    return sorted({(k - 1 if s == "k-1" else k if s == "k" else s) for s in list(CPU_SIZES) + list(extra)})
+
+
+# ---- numpy reference ------------------------------------------------------------------------------------------------
+_SH = np.arange(32, dtype=np.uint64) * np.uint64(2)
+
+
+def _reverse_codes(x):
+    """the 32 two-bit codes of each u64 in reverse order: swap codes inside bytes, then the bytes"""
+    x = ((x >> np.uint64(2)) & np.uint64(0x3333333333333333)) | ((x & np.uint64(0x3333333333333333)) << np.uint64(2))
+    x = ((x >> np.uint64(4)) & np.uint64(0x0F0F0F0F0F0F0F0F)) | ((x & np.uint64(0x0F0F0F0F0F0F0F0F)) << np.uint64(4))
+    return x.byteswap()
+
+
+def np_kmers(words, length, k, canonical=False):
+    """k-mer 32w+r = the 64-bit window of the packed words at nucleotide 32w+r (words w and w+1 shifted right by 2r codes'
+    worth of bits), masked to 2k bits; canonical: min with the reverse complement (complement, reverse the 32 codes, shift
+    the k codes down)."""
+    m = length - k + 1 if length >= k else 0
+    if m == 0:
+        return np.empty(0, dtype=np.uint64)
+    nw = (m + 31) // 32
+    w = np.zeros(nw + 1, dtype=np.uint64)
+    have = min((length + 31) // 32, nw + 1)
+    w[:have] = np.asarray(words, dtype=np.uint64)[:have]
+    lo, hi = w[:-1, None], w[1:, None]
+    x = (lo >> _SH) | np.where(_SH == 0, np.uint64(0), (hi << np.uint64(1)) << (np.uint64(63) - _SH))
+    x = x.reshape(-1)[:m]
+    x &= np.uint64((1 << (2 * k)) - 1)
+    if not canonical:
+        return x
+    rc = _reverse_codes(x ^ np.uint64(0xAAAAAAAAAAAAAAAA)) >> np.uint64(64 - 2 * k)
+    return np.minimum(x, rc)
+
+
+def ascii_kmers(oracle, s, k, canonical=False):
+    """the definition in letters: k-mer i = s[i:i+k] packed like a sequence of length k (oracle.n_to_bits_lut of the
+    letters, padded with 'A' = code 0 to one word); rc = the reverse complement of those letters, packed the same way"""
+    m = len(s) - k + 1 if len(s) >= k else 0
+    if m == 0:
+        return np.empty(0, dtype=np.uint64)
+
+    def pack(kmers):
+        return oracle.n_to_bits_lut(np.frombuffer(b"".join(x + b"A" * (32 - k) for x in kmers), dtype=np.uint8))
+
+    fwd = [s[i : i + k] for i in range(m)]
+    f = pack(fwd)
+    if not canonical:
+        return f
+    return np.minimum(f, pack([x.translate(COMP)[::-1] for x in fwd]))
+
+
+@pytest.mark.parametrize("k", KS)
+def test_numpy_reference_against_letters(oracle, k):
+    for n_len in _sizes(k):
+        s = oracle.fill_random_acgt(n_len, seed=1000 + n_len + k).tobytes()
+        words = oracle.np_n_to_bits_lut(np.frombuffer(s, dtype=np.uint8))
+        for canonical in (False, True):
+            want = ascii_kmers(oracle, s, k, canonical)
+            got = np_kmers(words, n_len, k, canonical)
+            assert got.dtype == np.uint64 and got.size == max(n_len - k + 1, 0)
+            assert np.array_equal(got, want), (n_len, k, canonical)
+        if n_len >= k:
+            # forward k-mer i decodes to the letters i..i+k-1; bits 2k..63 are zero
+            f = np_kmers(words, n_len, k)
+            for i in (0, n_len - k, (n_len - k) // 2):
+                assert bytes(oracle.bits_to_n_lut(f[i : i + 1], k)) == s[i : i + k]
+            assert k == 32 or not (f >> np.uint64(2 * k)).any()
+            # strand symmetry: canonical k-mer i of s == canonical k-mer m-1-i of revcomp(s)
+            rs = s.translate(COMP)[::-1]
+            rw = oracle.np_n_to_bits_lut(np.frombuffer(rs, dtype=np.uint8))
+            assert np.array_equal(np_kmers(words, n_len, k, True), np_kmers(rw, n_len, k, True)[::-1])
+            # bits beyond len in the last word are ignored
+            if n_len & 31:
+                g = words.copy()
+                g[-1] |= np.uint64(0xFFFFFFFFFFFFFFFF) << np.uint64(2 * (n_len & 31))
+                for canonical in (False, True):
+                    assert np.array_equal(np_kmers(g, n_len, k, canonical), np_kmers(words, n_len, k, canonical))
+
+
+def test_canonical_order_is_numeric_not_lexicographic(oracle):
+    """the header's one sentence: min() compares the LSB-first packed u64, not the letters"""
+    def canon(letters):
+        return np_kmers(oracle.n_to_bits_lut(np.frombuffer(letters, dtype=np.uint8)), len(letters), len(letters), True).tolist()
+
+    assert canon(b"CA") == [1]  # "CA" = 1 | 0 << 2, its reverse complement "TG" = 2 | 3 << 2 = 14
+    assert canon(b"AG") == canon(b"CT") == [9]  # "CT" = 1 | 2 << 2 = 9 < "AG" = 0 | 3 << 2 = 12, though "AG" < "CT" in letters
+
+
+# ---- ABI, no device needed ----------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def L():
+    from cute_nucleotides_amd import _lib, build
+
+    build.build()
+    return _lib.lib()
+
+
+def test_abi_errors_come_before_any_device_work(L):
+    from cute_nucleotides_amd import _lib
+
+    buf = np.zeros(4096, dtype=np.uint64)
+    base = buf.ctypes.data
+    q = lambda word, byte=0: ctypes.c_void_p(base + 8 * word + byte)  # noqa: E731
+    out = np.full(64, 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
+    o = lambda byte=0: ctypes.c_void_p(out.ctypes.data + byte)  # noqa: E731
+    for fn, tail in ((L.cnt_kmers, ()), (L.cnt_kmers_dev, (None,))):
+        call = lambda *a: fn(*(a + tail))  # noqa: E731
+        # k out of range, unknown flags -- even when there would be no k-mer
+        for k in (0, 33, 64):
+            assert call(q(0), 100, k, 0, o(), 64) == _lib.CNT_EINVAL, (fn, k)
+            assert call(None, 0, k, 0, None, 0) == _lib.CNT_EINVAL
+        for flags in (0x1, 0x2, 0x4, 0x8, 0x20, 0x80000000, CNT_KMER_CANONICAL | 0x1):
+            assert call(q(0), 100, 21, flags, o(), 64) == _lib.CNT_EINVAL, (fn, flags)
+        # NULL pointers when m > 0
+        assert call(None, 100, 21, 0, o(), 64) == _lib.CNT_EINVAL
+        assert call(q(0), 100, 21, 0, None, 64) == _lib.CNT_EINVAL
+        # pointers not 8-B aligned
+        for byte in (1, 4, 7):
+            assert call(q(0, byte), 100, 21, 0, o(), 64) == _lib.CNT_EINVAL
+            assert call(q(0), 100, 21, CNT_KMER_CANONICAL, o(byte), 64) == _lib.CNT_EINVAL
+        # output overlapping the input words (100 nt = 4 words at q(10)): inside, straddling either end, identical
+        for ow in (10, 12, 13, 8, 0):
+            assert call(q(10), 100, 21, 0, q(ow), 80) == _lib.CNT_EINVAL, (fn, ow)
+        # capacity: m = 80
+        assert call(q(10), 100, 21, 0, q(100), 79) == _lib.CNT_ECAP
+        assert call(q(0), 100, 1, 0, o(), 64) == _lib.CNT_ECAP  # m = 100 > 64
+        # len < k: zero k-mers, CNT_OK without a device, also with NULL pointers
+        assert call(None, 0, 1, 0, None, 0) == _lib.CNT_OK
+        assert call(None, 20, 21, CNT_KMER_CANONICAL, None, 0) == _lib.CNT_OK
+        assert call(q(0), 31, 32, 0, o(), 0) == _lib.CNT_OK
+    assert (out == 0x5A5A5A5A5A5A5A5A).all()  # nothing was written
+    count = ctypes.c_int(-1)
+    assert L.cnt_device_count(ctypes.byref(count)) == _lib.CNT_OK
+    if count.value == 0:
+        # past the argument checks a call needs a device (on a GPU box these would run on host pointers: only tried without one)
+        for flags in (0, CNT_KMER_CANONICAL):  # m = 84 - 21 + 1 = 64
+            assert L.cnt_kmers(q(0), 84, 21, flags, o(), 64) == _lib.CNT_ENODEV
+            assert L.cnt_kmers_dev(q(0), 84, 21, flags, o(), 64, None) < 0
+        assert (out == 0x5A5A5A5A5A5A5A5A).all()
+
+
+def test_python_wrappers_raise_value_error(L):
+    from cute_nucleotides_amd import packed_ops as po
+
+    w = np.zeros(2, dtype=np.uint64)
+    for k in (0, 33):
+        with pytest.raises(ValueError):
+            po.kmers_hip(w, 64, k)
+    with pytest.raises(ValueError):
+        po.kmers_hip(w, 65, 21)  # longer than the words hold
+    with pytest.raises(ValueError):
+        po.kmers_hip(w, 64, 21, out=np.empty(43, dtype=np.uint64))  # m = 44
+    assert po.kmers_hip(w, 20, 21).size == 0 and po.kmers_hip(w, 0, 1, canonical=True).size == 0
+
+
+def test_abi_wiring(L):
+    import subprocess
+
+    from cute_nucleotides_amd import _lib
+
+    for name in ("cnt_kmers", "cnt_kmers_dev"):
+        assert name in _lib.SIGNATURES
+        assert hasattr(L, name)
+    assert _lib.CNT_KMER_CANONICAL == CNT_KMER_CANONICAL
+    nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    exported = {line.split()[-1] for line in nm.splitlines() if " T " in line}
+    assert {"cnt_kmers", "cnt_kmers_dev"} <= exported
+    header = open(os.path.join(ROOT, "include", "cute_nt.h")).read()
+    assert "#define CNT_KMER_CANONICAL 0x10u" in header
+    for flag in ("CNT_STRICT_LUT 0x1u", "CNT_ALLOW_N 0x2u", "CNT_TAIL_LUT 0x4u", "CNT_SPREAD_COUNT 0x8u"):
+        assert flag in header  # the new bit is distinct from every existing flag
+
+
+KMER_KERNELS = ["void cnt::kmer_tiles<256, 2, false>", "void cnt::kmer_tiles<256, 2, true>", "void cnt::kmer_generic<false>", "void cnt::kmer_generic<true>"]
+
+
+def test_kmer_kernels_isa():
+    sys.path.insert(0, os.path.join(ROOT, "bench"))
+    import isa_digest
+
+    found = isa_digest.kernels(isa_digest.assembly())
+    for name in KMER_KERNELS:
+        assert name in found, name
+        e = found[name]
+        body = e["body"]
+        assert not [i for i in body if "scratch_" in i], name
+        assert not [i for i in body if "s_xor_b64 exec, exec" in i], name
+        assert e["meta"]["private_segment_fixed_size"] == 0 and e["meta"]["next_free_vgpr"] <= 84, (name, e["meta"])
+    for name in KMER_KERNELS[:2]:
+        stores = [i for i in found[name]["body"] if "_store" in i]
+        assert stores and all(i.startswith("buffer_store_dwordx4") for i in stores), stores
+        assert all("sc0" in i and "sc1" in i and " nt" in i for i in stores), stores  # the codec tiles' write-through policy
+    assert len(found) < 60, len(found)
+
+
+# ---------------------------------------------------------------------------------------------------------- GPU part
+gpu = pytest.mark.gpu
+GPU_EXTRA = [32 * 8192 + 7, (1 << 22) + 13, 3 * (1 << 21) + 64]
+
+
+def _random_words(rng, n_len, extra=0):
+    return rng.integers(0, 2**64, (n_len + 31) // 32 + extra, dtype=np.uint64)  # garbage above len in the last word included
+
+
+@gpu
+@pytest.mark.parametrize("k", KS)
+def test_gpu_kmers_match_reference(k):
+    import torch
+
+    from cute_nucleotides_amd import packed_ops as po
+
+    rng = np.random.default_rng(k)
+    for n_len in _sizes(k, GPU_EXTRA):
+        w = _random_words(rng, n_len)
+        d = torch.from_numpy(w.view(np.int64)).cuda()
+        for canonical in (False, True):
+            want = np_kmers(w, n_len, k, canonical)
+            assert np.array_equal(po.kmers_hip(w, n_len, k, canonical=canonical), want), (n_len, k, canonical, "host")
+            got = po.kmers_dev(d, n_len, k, canonical=canonical)
+            assert got.numel() == want.size
+            assert np.array_equal(got.cpu().numpy().view(np.uint64), want), (n_len, k, canonical, "device")
+
+
+@gpu
+def test_gpu_kmers_pointer_phases_and_edges():
+    """input and output views at word offsets 0..3 (every 16-B phase pairing), garbage above len, a sentinel around and
+    behind the m k-mers that must survive"""
+    import torch
+
+    from cute_nucleotides_amd import packed_ops as po
+
+    rng = np.random.default_rng(77)
+    sentinel = -0x3C3C3C3C3C3C3C3D
+    lens = [32 * 40 + 17, 32 * 100, 32 * 100 + 1, 512 * 3 + 31, 512 * 5 + 32 * 3 + 5, 32 * 2048 + 19]
+    top = max(lens) // 32 + 8
+    w = rng.integers(0, 2**64, top, dtype=np.uint64)
+    obuf = torch.empty(max(lens) + 64, dtype=torch.int64, device="cuda")
+    for k in (1, 17, 31, 32):
+        for canonical in (False, True):
+            for n_len in lens:
+                m = n_len - k + 1
+                nw = (n_len + 31) // 32
+                for pi in range(4):
+                    src = w[pi : pi + nw].copy()
+                    src[-1] |= np.uint64(0xFFFFFFFFFFFFFFFF) << np.uint64(2 * (n_len & 31)) if n_len & 31 else np.uint64(0)
+                    dsrc = torch.from_numpy(src.view(np.int64)).cuda()
+                    big = torch.empty(nw + 4, dtype=torch.int64, device="cuda")
+                    big[pi : pi + nw] = dsrc  # the input as a view at word offset pi
+                    want = np_kmers(src, n_len, k, canonical)
+                    for po_ in range(4):
+                        obuf.fill_(sentinel)
+                        view = obuf[8 + po_ : 8 + po_ + m + 5]
+                        got = po.kmers_dev(big[pi : pi + nw], n_len, k, canonical=canonical, out=view)
+                        assert got.data_ptr() == view.data_ptr()
+                        o = obuf.cpu().numpy()
+                        assert (o[: 8 + po_] == sentinel).all() and (o[8 + po_ + m :] == sentinel).all(), (k, n_len, pi, po_)
+                        assert np.array_equal(o[8 + po_ : 8 + po_ + m].view(np.uint64), want), (k, canonical, n_len, pi, po_)
+
+
+@gpu
+def test_gpu_kmers_pinned_host_buffers():
+    import cute_nucleotides_amd as cn
+    from cute_nucleotides_amd import packed_ops as po
+
+    rng = np.random.default_rng(5)
+    for n_len, k in ((32 * 4096 + 9, 31), (1000, 17), ((1 << 20) + 3, 21)):
+        m = n_len - k + 1
+        bits = cn.pinned_empty((n_len + 31) // 32, np.uint64)
+        bits[:] = _random_words(rng, n_len)
+        out = cn.pinned_empty(m + 7, np.uint64)
+        assert cn.is_pinned(bits) and cn.is_pinned(out)
+        for canonical in (False, True):
+            out[:] = 0xDEADBEEFDEADBEEF
+            got = po.kmers_hip(bits, n_len, k, canonical=canonical, out=out)
+            assert np.array_equal(got, np_kmers(bits, n_len, k, canonical)), (n_len, k, canonical)
+            assert (out[m:] == 0xDEADBEEFDEADBEEF).all()
+            # pinned input, pageable output (staged) agrees
+            assert np.array_equal(po.kmers_hip(bits, n_len, k, canonical=canonical), got)
+
+
+def _device_sequence(n_len, seed):
+    import torch
+
+    import cute_nucleotides_amd as cn
+    from cute_nucleotides_amd import devutil
+
+    n = torch.empty(n_len, dtype=torch.uint8, device="cuda")
+    devutil.fill_random_acgt(n, seed)
+    bits = cn.n_to_bits_dev(n)
+    del n
+    return bits
+
+
+@gpu
+def test_gpu_kmers_strand_symmetry():
+    """canonical k-mer i of s == canonical k-mer m-1-i of revcomp(s), on the device at 2^30+5 nt"""
+    import torch
+
+    from conftest import need_free_hbm
+    from cute_nucleotides_amd import packed_ops as po
+
+    n_len, k = (1 << 30) + 5, 31
+    need_free_hbm(28)
+    bits = _device_sequence(n_len, 11)
+    rc = po.reverse_complement_dev(bits, n_len)
+    a = po.kmers_dev(bits, n_len, k, canonical=True)
+    b = po.kmers_dev(rc, n_len, k, canonical=True)
+    assert a.numel() == n_len - k + 1
+    assert torch.equal(a, torch.flip(b, (0,)))
+    # not vacuous: the canonical k-mers are not the forward ones
+    assert not torch.equal(a[:2018], po.kmers_dev(bits[:64], 2048, k))
+
+
+def _host_checksum(oracle, n_len, k, canonical, seed, chunk=1 << 24):
+    """oracle.checksum_words of the whole expected output, chunk by chunk: chunk c holds k-mers [c*chunk, (c+1)*chunk) and
+    needs nucleotides [c*chunk, (c+1)*chunk + k - 1) -- regenerated by the oracle's counter-based generator.  The checksum
+    is a sum over words, so the chunks add up in any order (a few threads: numpy and the oracle release the GIL)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    m = n_len - k + 1
+
+    def one(first):
+        mc = min(chunk, m - first)
+        s = oracle.fill_random_acgt(mc + k - 1, seed, first_nt=first)
+        return oracle.checksum_words(np_kmers(oracle.n_to_bits_lut(s), mc + k - 1, k, canonical), first_word=first)
+
+    with ThreadPoolExecutor(6) as pool:
+        return sum(pool.map(one, range(0, m, chunk))) & 0xFFFFFFFFFFFFFFFF
+
+
+@gpu
+@pytest.mark.parametrize("n_len,k,canonical", [((1 << 31) + 17, 31, True), ((1 << 32) + 33, 17, False)], ids=["2^31+17-k31-canonical", "2^32+33-k17-forward"])
+def test_gpu_kmers_full_size(oracle, fullsize, n_len, k, canonical):
+    """the whole output against the host checksum; m > 2^32 in the second case (64-bit indexing); one changed word is seen"""
+    import torch
+
+    import stream_checks
+    from conftest import need_free_hbm
+    from cute_nucleotides_amd import devutil, packed_ops as po
+
+    m = n_len - k + 1
+    need_free_hbm((m * 8 + n_len + (n_len >> 2)) // (1 << 30) + 2)
+    seed = 0x6B6D6572 + k
+    bits = _device_sequence(n_len, seed)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = po.kmers_dev(bits, n_len, k, canonical=canonical)
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t0) * 1e3
+    assert out.numel() == m
+    got = devutil.checksum_words(out)
+    t1 = time.perf_counter()
+    want = _host_checksum(oracle, n_len, k, canonical, seed)
+    fullsize(n_len.bit_length() - 1, ms, check="kmers k=%d %s: full-length host checksum (%.0f s)" % (k, "canonical" if canonical else "forward", time.perf_counter() - t1))
+    assert got == want, "kmers k=%d canonical=%s: checksum %#x != host %#x" % (k, canonical, got, want)
+    stream_checks.assert_mutation_seen(out, m - 3, want)
+    stream_checks.assert_mutation_seen(out, (m * 5) // 7, want)
