@@ -219,3 +219,21 @@ uint64_t cnt_oracle_validate(const uint8_t *n, size_t n_len, int allow_n) {
     }
     return bad;
 }
+
+/* k-mers (include/cute_nt.h "k-mers"; not in the reference either).  Rolling values, one 2-bit code per step and never
+ * a 64-bit window of the packed words: after code i, `fwd` holds codes i-k+1..i with the oldest in bits 0-1 (shift out
+ * the oldest at the bottom, put the new one in at code k-1), `rc` holds their complements in reverse order (shift up,
+ * complement of the new code at the bottom, mask to 2k bits).  out[i-k+1] is written once k codes are in. */
+int cnt_oracle_kmers(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *out) {
+    if (k == 0 || k > 32 || (flags & ~CNT_ORACLE_KMER_CANONICAL)) return CNT_ORACLE_EARG;
+    const int canonical = (flags & CNT_ORACLE_KMER_CANONICAL) != 0;
+    const uint64_t mask = k == 32 ? ~0ull : (1ull << (2 * k)) - 1;
+    uint64_t fwd = 0, rc = 0;
+    for (size_t i = 0; i < len; i++) {
+        const uint64_t c = code_at(bits, i);
+        fwd = (fwd >> 2) | (c << (2 * (k - 1)));
+        rc = ((rc << 2) | (c ^ 2u)) & mask;
+        if (i + 1 >= k) out[i + 1 - k] = canonical && rc < fwd ? rc : fwd;
+    }
+    return CNT_ORACLE_OK;
+}

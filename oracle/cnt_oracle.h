@@ -33,6 +33,7 @@ extern "C" {
 #define CNT_ORACLE_ELEN 1 /* "The length is greater than the number of nucleotides!" */
 #define CNT_ORACLE_ECAP 2 /* caller's output buffer too small */
 #define CNT_ORACLE_ECPU 3 /* SIMD port called on a CPU without AVX2/BMI2/PCLMUL */
+#define CNT_ORACLE_EARG 4 /* k-mers: k outside 1..32 or an unknown flag */
 
 /* ceil(n_len/32): words produced by every 2-bit encoder (n_to_bits.rs:35,83). */
 size_t cnt_oracle_words_for(size_t n_len);
@@ -82,6 +83,10 @@ uint64_t cnt_oracle_hamming(const uint64_t *a, const uint64_t *b, size_t len);
 void cnt_oracle_complement(const uint64_t *bits, size_t len, uint64_t *out);
 void cnt_oracle_reverse_complement(const uint64_t *bits, size_t len, uint64_t *out);
 uint64_t cnt_oracle_validate(const uint8_t *n, size_t n_len, int allow_n);
+/* k-mers, 1 <= k <= 32: out[i] for i < len-k+1 (nothing when len < k), forward or with CNT_ORACLE_KMER_CANONICAL the
+ * smaller u64 of it and its reverse complement -- rolled one code at a time, no 64-bit window of the words. */
+#define CNT_ORACLE_KMER_CANONICAL 0x10u /* == CNT_KMER_CANONICAL */
+int cnt_oracle_kmers(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *out);
 
 /* Reference-faithful timing: seconds per call with the output malloc'ed and freed
  * INSIDE the timed call, as benches/bench_n_to_bits.rs:6-7 demands.

@@ -77,6 +77,8 @@ def lib():
         L.cnt_oracle_reverse_complement.restype = None
         L.cnt_oracle_validate.argtypes = [u8p, sz, ctypes.c_int]
         L.cnt_oracle_validate.restype = ctypes.c_uint64
+        L.cnt_oracle_kmers.argtypes = [u64p, sz, ctypes.c_uint, ctypes.c_uint, u64p]
+        L.cnt_oracle_kmers.restype = ctypes.c_int
         L.cnt_port_time_alloc_inclusive.argtypes = [ctypes.c_int, ctypes.c_void_p, sz, ctypes.c_int]
         L.cnt_port_time_alloc_inclusive.restype = ctypes.c_double
         L.cnt_oracle_fill_random_acgt.argtypes = [u8p, sz, sz, ctypes.c_uint64]
@@ -215,6 +217,23 @@ def reverse_complement(bits, length):
 def validate(n, allow_n=False):
     n = _as_u8(n)
     return int(lib().cnt_oracle_validate(_ptr(n), n.size, 1 if allow_n else 0))
+
+
+KMER_CANONICAL = 0x10  # == CNT_KMER_CANONICAL
+
+
+def kmers(bits, length, k, canonical=False):
+    """the length-k+1 k-mers of the first `length` codes of `bits` (np.uint64; none when length < k), forward or canonical:
+    the scalar definition, rolled one code at a time (cnt_oracle_kmers)"""
+    if not 1 <= k <= 32:
+        raise ValueError("k must be in 1..32")
+    bits = np.ascontiguousarray(bits, dtype=np.uint64)
+    if length > bits.size * 32:
+        raise ValueError(ELEN_MESSAGE)
+    out = np.empty(max(length - k + 1, 0), dtype=np.uint64)
+    if out.size:
+        _check(lib().cnt_oracle_kmers(_ptr(bits), length, k, KMER_CANONICAL if canonical else 0, _ptr(out)))
+    return out
 
 
 # ---- generator + checksum ---------------------------------------------------------
@@ -367,3 +386,20 @@ def stream_validate(seed, n_len, first_nt=0, plants=(), allow_n=False, per_chunk
     counts = _run(lambda lo, m: validate(_stream_ascii(False, seed, first_nt, lo, m, pl), allow_n=allow_n),
                   _chunks(n_len, chunk_nt, 1), workers)
     return counts if per_chunk else sum(counts)
+
+
+def stream_kmers_checksum(seed, n_len, k, canonical, first_nt=0, per_chunk=False, chunk_nt=None, workers=None):
+    """checksum_words of the k-mers (kmers()) of the fill_random_acgt stream of n_len nt at `first_nt` (any nt), salted
+    with the k-mer index: the value devutil.checksum_words(out) of the whole k-mer output has to give.  Chunk [lo, lo + m)
+    of the k-mers is made from nt [lo, lo + m + k - 1) of the stream.  per_chunk=True returns the list of per-chunk
+    checksums instead (chunks of `chunk_nt` k-mers; any chunk size: a k-mer is one output word)."""
+    if not 1 <= k <= 32:
+        raise ValueError("k must be in 1..32")
+    none = _plants(())
+
+    def chunk(lo, m):
+        x = n_to_bits_lut(_stream_ascii(False, seed, first_nt, lo, m + k - 1, none))
+        return checksum_words(kmers(x, m + k - 1, k, canonical), first_word=lo)
+
+    sums = _run(chunk, _chunks(max(n_len - k + 1, 0), chunk_nt, 1), workers)
+    return sums if per_chunk else sum(sums) % (1 << 64)

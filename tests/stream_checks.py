@@ -105,3 +105,35 @@ def assert_mutation_seen(words, index, want, first_word=0):
     finally:
         w.bitwise_xor_(1 << 41)
     assert devutil.checksum_words(words, first_word=first_word) == want
+
+
+def check_kmers(out, seed, n_len, k, canonical, label="", record=None, want=None, workers=16):
+    """devutil.checksum_words(out) == oracle.stream_kmers_checksum(...): `out` is the whole k-mer output (an int64 CUDA
+    tensor, any 8-B phase) of the fill_random_acgt stream of n_len nt.  On a mismatch the per-chunk checksums name the
+    first chunk of k-mers that differs.  Returns the expected checksum; `record` and `want` as in check_words."""
+    from cute_nucleotides_amd import devutil
+    from oracle import cnt_oracle as orc
+
+    label = label or "kmers k=%d %s" % (k, "canonical" if canonical else "forward")
+    t0 = time.perf_counter()
+    if want is None:
+        want = orc.stream_kmers_checksum(seed, n_len, k, canonical, workers=workers)
+    got = devutil.checksum_words(out)
+    if record is not None:
+        record(n_len.bit_length() - 1, (time.perf_counter() - t0) * 1e3, check="full-length oracle: " + label)
+    if got != want:
+        pytest.fail("%s: full-length checksum %#x != oracle %#x; %s" % (label, got, want, first_bad_kmer_chunk(out, seed, n_len, k, canonical, workers)))
+    return want
+
+
+def first_bad_kmer_chunk(out, seed, n_len, k, canonical, workers=16):
+    """names the first chunk of STREAM_CHUNK_NT k-mers whose device checksum differs from the oracle's"""
+    from cute_nucleotides_amd import devutil
+    from oracle import cnt_oracle as orc
+
+    kc = orc.STREAM_CHUNK_NT
+    per = orc.stream_kmers_checksum(seed, n_len, k, canonical, per_chunk=True, workers=workers)
+    for c, want in enumerate(per):
+        if devutil.checksum_words(out[c * kc : (c + 1) * kc], first_word=c * kc) != want:
+            return "first differing chunk %d of %d: k-mers [%d, %d)" % (c, len(per), c * kc, min((c + 1) * kc, out.numel()))
+    return "no chunk differs on its own (k-mers beyond the output?)"

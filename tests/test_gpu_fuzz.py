@@ -332,3 +332,41 @@ def test_validated_encoders_fuzz(oracle, small_nt, seed):
         n5 = _dirty(rng, alpha5, n_len)
         w5, bad5 = n2.n_to_bits2_hip_checked(n5, strict_lut=strict)
         assert np.array_equal(w5, n2.n_to_bits2_hip(n5, strict_lut=strict)) and bad5 == oracle.validate(n5, allow_n=True), (seed, n_len, strict)
+
+
+@pytest.mark.parametrize("seed", range(3 * SEEDS))
+def test_kmers_fuzz(oracle, seed):
+    """k-mers on random lengths, k = 1..32, both modes, the input view at word phase 0..3 and the output at 8-B phase 0..15
+    of a 128-B line (every head), guards around the output; the host tier on the same input in the same iteration, staged
+    or through pinned buffers -- against the scalar oracle"""
+    import torch
+
+    import cute_nucleotides_amd as cn
+    from cute_nucleotides_amd import packed_ops as po
+
+    rng = np.random.default_rng(1300 + seed)
+    for n_len in _lengths(rng, 16):
+        k, canonical = int(rng.integers(1, 33)), bool(rng.integers(0, 2))
+        pi, phase = int(rng.integers(0, 4)), int(rng.integers(0, 16))
+        nw = (n_len + 31) // 32
+        w = rng.integers(0, 2**64, nw + 4, dtype=np.uint64)  # garbage above len and past the view
+        want = oracle.kmers(w[pi : pi + nw], n_len, k, canonical)
+        m = want.size
+        tag = (seed, n_len, k, canonical, pi, phase)
+        d = torch.from_numpy(w.view(np.int64)).cuda()
+        obuf = torch.full((m + 32,), -1, dtype=torch.int64, device="cuda")
+        assert obuf.data_ptr() % 128 == 0
+        got = po.kmers_dev(d[pi : pi + nw], n_len, k, canonical=canonical, out=obuf[phase : phase + m])
+        assert got.numel() == m
+        o = obuf.cpu().numpy()
+        assert np.array_equal(o[phase : phase + m].view(np.uint64), want), tag
+        assert (o[:phase] == -1).all() and (o[phase + m :] == -1).all(), tag
+        if rng.integers(0, 2) and m:
+            bits = cn.pinned_empty(nw, np.uint64)
+            bits[:] = w[pi : pi + nw]
+            out = cn.pinned_empty(m + 3, np.uint64)
+            out[:] = 0xDEADBEEFDEADBEEF
+            assert np.array_equal(po.kmers_hip(bits, n_len, k, canonical=canonical, out=out), want), tag + ("pinned",)
+            assert (out[m:] == 0xDEADBEEFDEADBEEF).all(), tag
+        else:
+            assert np.array_equal(po.kmers_hip(w[pi : pi + nw], n_len, k, canonical=canonical), want), tag + ("staged",)

@@ -5,7 +5,7 @@ A kernel launch takes at most 2^31-1 threads, so the launchers cut very large bu
 encoder and never for most others, so the loops, and the rule that a call's edge work (head words, ragged end) rides in the
 LAST launch only, were exercised by two 64-GiB tests at best.  The tuning key "launch_tiles" lowers the limit: here every
 tier runs with 64 and 128 tiles per launch against the oracle, at aligned and misaligned pointers, and a captured graph
-confirms that the calls really were cut."""
+confirms that the calls really were cut.  k-mer extraction takes its first launch past 2^33 k-mers; here after 64 tiles."""
 import numpy as np
 import pytest
 
@@ -159,3 +159,34 @@ def test_packed_ops_in_several_launches(oracle, launch_tiles, persistent):
     for off in (0, 1, 127):
         for allow in (False, True):
             assert int(po.validate_dev(d[off:], allow_n=allow).item()) == oracle.validate(n[off:], allow_n=allow)
+
+
+@pytest.mark.parametrize("canonical", [False, True])
+def test_kmers_in_several_launches(oracle, launch_tiles, canonical):
+    """k-mers over 3 launches' worth of tiles + 17 tiles + an odd tail, with the output at heads 0 and 13, k in {1, 17,
+    32}: against the scalar oracle with sentinels around the output, and the captured graph holds exactly the launches
+    of the launcher's plan (ceil(tiles / launch_tiles) + (head > 0) + (tail > 0))"""
+    import torch
+
+    from cute_nucleotides_amd import packed_ops as po
+    from test_kmers import KMERS_PER_TILE, SENTINEL, kmer_plan
+
+    rng = np.random.default_rng(launch_tiles + canonical)
+    for k in (1, 17, 32):
+        for head in (0, 13):
+            m = head + (3 * launch_tiles + 17) * KMERS_PER_TILE + 333
+            n_len = m + k - 1
+            w = rng.integers(0, 2**64, (n_len + 31) // 32, dtype=np.uint64)
+            want = oracle.kmers(w, n_len, k, canonical)
+            d = torch.from_numpy(w.view(np.int64)).cuda()
+            obuf = torch.full((m + 64,), SENTINEL, dtype=torch.int64, device="cuda")
+            assert obuf.data_ptr() % 128 == 0
+            o0 = 16 + (16 - head) % 16
+            view = obuf[o0 : o0 + m]
+            plan = kmer_plan(view.data_ptr(), n_len, k, launch_tiles)
+            assert plan == (head, 3 * launch_tiles + 17, 333, 4 + (head > 0) + 1), (k, head, plan)
+            po.kmers_dev(d, n_len, k, canonical=canonical, out=view)
+            o = obuf.cpu().numpy()
+            assert (o[:o0] == SENTINEL).all() and (o[o0 + m :] == SENTINEL).all(), (k, head)
+            assert np.array_equal(o[o0 : o0 + m].view(np.uint64), want), (k, head, canonical)
+            assert _kernel_nodes_of(torch, lambda: po.kmers_dev(d, n_len, k, canonical=canonical, out=view)) == plan[3], (k, head)

@@ -167,3 +167,63 @@ def test_per_chunk_checksum_sees_a_swap_and_a_bit_flip(oracle):
         s3 = chunk_sums(w3)
         assert sum(s3) % (1 << 64) != total
         assert [c for c in range(len(per)) if s3[c] != per[c]] == [2]
+
+
+# ---- k-mers: stream_kmers_checksum, the whole-output value of the full-size k-mer tests ----------------------------------
+def _direct_kmers(oracle, seed, n_len, k, canonical, first_nt=0):
+    """the k-mers of the whole stream in one oracle call; any first_nt (generated from the word boundary below, sliced)"""
+    g0 = first_nt & ~31
+    n = oracle.fill_random_acgt(n_len + first_nt - g0, seed, first_nt=g0)[first_nt - g0 :]
+    return oracle.kmers(oracle.n_to_bits_lut(n), n_len, k, canonical)
+
+
+@pytest.mark.parametrize("k", [1, 2, 17, 31, 32])
+@pytest.mark.parametrize("canonical", [False, True])
+def test_stream_kmers_checksum_equals_the_direct_oracle_call(oracle, k, canonical):
+    """chunk c of the k-mers is made from nt [lo, lo + m + k - 1): forced tiny chunks put the chunk boundaries inside
+    k-mers (and, for k > chunk, several boundaries inside one k-mer), at word starts 0, 32*w and off the word grid"""
+    for n_len in (0, k - 1, k, k + 1, 31, 32, 33, 32 * 40 + 17, 100003):
+        for first_nt in (0, 32 * 12345, 45):
+            want = _direct_kmers(oracle, 0x5EED + k, n_len, k, canonical, first_nt)
+            total = oracle.checksum_words(want)
+            for chunk_nt in (None, 1, 7, 33, 1000):
+                if chunk_nt is not None and chunk_nt * 200 < n_len:
+                    continue  # a few hundred chunks at most
+                got = oracle.stream_kmers_checksum(0x5EED + k, n_len, k, canonical, first_nt=first_nt, chunk_nt=chunk_nt)
+                assert got == total, (k, canonical, n_len, first_nt, chunk_nt)
+            per = oracle.stream_kmers_checksum(0x5EED + k, n_len, k, canonical, first_nt=first_nt, per_chunk=True, chunk_nt=33)
+            assert per == [oracle.checksum_words(want[c * 33 : (c + 1) * 33], first_word=c * 33) for c in range(len(per))]
+            assert len(per) == -(-want.size // 33) and sum(per) % (1 << 64) == total
+
+
+def test_stream_kmers_worker_count_does_not_change_the_result(oracle):
+    n_len = 32 * 3000 + 19
+    for k, canonical in ((1, False), (32, True), (21, True)):
+        vals = {w: oracle.stream_kmers_checksum(3, n_len, k, canonical, first_nt=32 * 5, per_chunk=True, chunk_nt=999, workers=w)
+                for w in (1, 3, 16)}
+        assert vals[1] == vals[3] == vals[16] and len(vals[1]) == -(-(n_len - k + 1) // 999), (k, canonical)
+
+
+def test_stream_kmers_per_chunk_sums_see_a_swap(oracle):
+    """the per-chunk checksums add up to the total, and two swapped k-mers -- inside one chunk or across chunks -- change
+    the total and exactly the chunks touched; forward and canonical streams differ"""
+    n_len, k, kc = 32 * 2000 + 7, 31, 32 * 250 + 3
+    want = _direct_kmers(oracle, 12, n_len, k, True)
+    per = oracle.stream_kmers_checksum(12, n_len, k, True, per_chunk=True, chunk_nt=kc)
+    total = oracle.stream_kmers_checksum(12, n_len, k, True)
+    assert sum(per) % (1 << 64) == total == oracle.checksum_words(want)
+
+    def chunk_sums(x):
+        return [oracle.checksum_words(x[c * kc : (c + 1) * kc], first_word=c * kc) for c in range(len(per))]
+
+    assert chunk_sums(want) == per
+    for i, j in ((10, 11), (kc - 1, kc), (5, 3 * kc + 5)):
+        assert want[i] != want[j]
+        w2 = want.copy()
+        w2[[i, j]] = w2[[j, i]]
+        s2 = chunk_sums(w2)
+        assert sum(s2) % (1 << 64) != total
+        assert {c for c in range(len(per)) if s2[c] != per[c]} == {i // kc, j // kc}
+    assert oracle.stream_kmers_checksum(12, n_len, k, False) != total
+    with pytest.raises(ValueError):
+        oracle.stream_kmers_checksum(12, n_len, 33, False)
