@@ -109,6 +109,9 @@ SIGNATURES = {
     "cnt_validate": (_int, [_vp, _sz, _uint, ctypes.POINTER(_u64)]),
     "cnt_kmers_dev": (_int, [_vp, _sz, _uint, _uint, _vp, _sz, _vp]),
     "cnt_kmers": (_int, [_vp, _sz, _uint, _uint, _vp, _sz]),
+    "cnt_minimizers_work_bytes": (_int, [_sz, _uint, _uint, ctypes.POINTER(_sz)]),
+    "cnt_minimizers_dev": (_int, [_vp, _sz, _uint, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_minimizers": (_int, [_vp, _sz, _uint, _uint, _uint, _vp, _vp, _sz, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

@@ -1,5 +1,5 @@
 """Operations on 2-bit packed nucleotides without decoding: Hamming distance,
-complement, reverse complement, k-mer extraction (forward and canonical), and alphabet validation of ASCII buffers.  The reference does
+complement, reverse complement, k-mer extraction (forward and canonical), (w,k)-minimizers, and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -7,6 +7,7 @@ import ctypes
 
 import numpy as np
 
+from . import _lib
 from ._lib import check, lib
 from .n_to_bits import _counter, _dev_guard, _enqueue, _out_words, _p, _u8, _u64
 
@@ -66,6 +67,35 @@ def kmers_hip(bits, length, k, canonical=False, out=None):
     return out[:m]
 
 
+def _n_windows(length, k, w):
+    if not 1 <= w <= 256:
+        raise ValueError("w must be in 1..256")
+    m = _n_kmers(length, k)
+    return m - w + 1 if m >= w else 0
+
+
+def minimizers_hip(bits, length, k, w, canonical=False, values=True):
+    """The (w,k)-minimizers of the sequence (include/cute_nt.h "k-mers"): in each window of w consecutive k-mers the
+    position with the smallest (fmix64(k-mer), position), each distinct position once, ascending.  Returns numpy uint64
+    (pos, val) of length n, val the k-mers at pos (forward, or canonical with canonical=True), or None with values=False.
+    The output buffers start at a guess of n and are sized to the reported n once if the guess was short."""
+    bits = _u64(bits)
+    _need(bits, length)
+    n_win = _n_windows(length, k, w)
+    cap = min(n_win, 2 * n_win // (w + 1) + n_win // 16 + 64)  # a random sequence selects ~2/(w+1) of its windows
+    flags = CNT_KMER_CANONICAL if canonical else 0
+    for attempt in range(2):
+        pos = np.empty(cap, dtype=np.uint64)
+        val = np.empty(cap, dtype=np.uint64) if values else None
+        n = ctypes.c_uint64(0)
+        rc = lib().cnt_minimizers(_p(bits), length, k, w, flags, _p(pos), _p(val) if values else None, cap, ctypes.byref(n))
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            cap = n.value
+            continue
+        check(rc)
+        return pos[: n.value], (val[: n.value] if values else None)
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -122,6 +152,46 @@ def kmers_dev(bits, length, k, canonical=False, out=None):
     _enqueue(bits, lib().cnt_kmers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
              ctypes.c_void_p(out.data_ptr()), out.numel())
     return out[:m]
+
+
+def minimizers_work_bytes(length, k, w):
+    """bytes of device scratch cnt_minimizers_dev needs for this call (0 when there is no window)"""
+    out = ctypes.c_size_t(0)
+    check(lib().cnt_minimizers_work_bytes(length, k, w, ctypes.byref(out)))
+    return out.value
+
+
+def minimizers_dev(bits, length, k, w, canonical=False, values=True, pos=None, val=None, work=None, count=None):
+    """Device tier of minimizers_hip, enqueued on torch's current stream without a synchronisation: returns (pos, val,
+    count), int64 CUDA tensors, count a 1-element tensor that the call SETS to n; pos[:n] / val[:n] are the result once the
+    stream has run (val is None with values=False).  Without `pos` / `val` they hold W = m-w+1 entries, the most n can be;
+    given ones of any capacity receive the first min(n, capacity) entries.  `work` (>= minimizers_work_bytes bytes, any
+    contents) and `count` may be reused across calls, e.g. in a captured graph."""
+    torch = _dev_guard(bits)
+    if bits.dtype != torch.int64:
+        raise TypeError("packed words must be an int64 tensor")
+    if length > bits.numel() * 32:
+        raise ValueError("The length is greater than the number of nucleotides!")
+    n_win = _n_windows(length, k, w)
+    # a given pos / val may hold fewer than W entries (the first min(n, capacity) are written); val at least as many as pos
+    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(n_win, 1), dtype=torch.int64, device=bits.device)
+    if values:
+        val = _out_words(torch, val, pos.numel(), bits) if val is not None else torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
+    elif val is not None:
+        raise ValueError("val given with values=False")
+    count = _out_words(torch, count, 1, bits)
+    need = minimizers_work_bytes(length, k, w)
+    if work is None:
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
+    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
+        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
+    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    pos_p = pos.data_ptr() or count.data_ptr()
+    val_p = (val.data_ptr() or count.data_ptr()) if values else None
+    _enqueue(bits, lib().cnt_minimizers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, w, CNT_KMER_CANONICAL if canonical else 0,
+             ctypes.c_void_p(pos_p), ctypes.c_void_p(val_p) if values else None, pos.numel(),
+             ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
+    return pos, (val if values else None), count
 
 
 def validate_dev(n, allow_n=False, acc=None):

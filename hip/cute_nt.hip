@@ -783,3 +783,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 
 #include "packed_ops_abi.inc"
 #include "kmer_abi.inc"
+#include "minimizer_abi.inc"

@@ -377,6 +377,32 @@ int cnt_validate(const uint8_t *n, size_t n_len, unsigned flags, uint64_t *inval
 int cnt_kmers_dev(const void *d_bits, size_t len, unsigned k, unsigned flags, void *d_out, size_t out_cap, void *stream);
 int cnt_kmers(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *out, size_t out_cap);
 
+/* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
+ *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m
+ *   h_i   = fmix64(x_i), the splitmix64 finaliser mod 2^64: z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9,
+ *           z = (z ^ (z >> 27)) * 0x94D049BB133111EB, h = z ^ (z >> 31) -- a bijection, so equal hashes mean equal k-mers
+ *   windows t = 0 .. W-1, W = m-w+1 (none when len < k or m < w); p(t) = the i in [t, t+w) with the smallest (h_i, i):
+ *           on equal hashes the leftmost position wins
+ *   output: the n distinct values of p(t) in ascending order (p(0), then each p(t) != p(t-1)); n <= W.  Entry j is
+ *           pos[j] (u64) and, when val is not NULL, val[j] = x_pos[j] (u64).
+ * Not minimap2's minimizers: another hash, palindromic k-mers (fwd == rc, even k) are not skipped, and there are no
+ * partial windows at either end.
+ * Errors, before any device work: k, w or flags out of range; when W > 0: a NULL or not 8-B aligned bits, pos or count, a
+ * val not 8-B aligned, pos or val overlapping the input words or each other; work_bytes below the query's answer:
+ * CNT_EINVAL.  W == 0: CNT_OK with the count set to 0 (when a count pointer is given).
+ * cnt_minimizers_work_bytes: the device scratch cnt_minimizers_dev needs (0 when W == 0; d_work may then be NULL).
+ * Device tier: enqueue-only (three kernels, no allocation, capturable in a graph), pointers at any 8-B phase, d_work any
+ *   caller scratch that nobody needs zeroed.  *d_count (device u64) is SET to n -- unlike the counters of cnt_hamming_dev and
+ *   the other reductions, which add to a caller-zeroed counter.  Entries j < min(n, out_cap) are written and nothing
+ *   past them: a caller whose buffer was too small reads n and calls again.
+ * Host tier: synchronous; pinned bits, pos and val are used in place.  *count = n always; when n > out_cap the first
+ *   out_cap entries are written and the call returns CNT_ECAP -- unlike elsewhere, this CNT_ECAP comes after the work. */
+int cnt_minimizers_work_bytes(size_t len, unsigned k, unsigned w, size_t *bytes);
+int cnt_minimizers_dev(const void *d_bits, size_t len, unsigned k, unsigned w, unsigned flags, void *d_pos, void *d_val,
+                       size_t out_cap, void *d_count, void *d_work, size_t work_bytes, void *stream);
+int cnt_minimizers(const uint64_t *bits, size_t len, unsigned k, unsigned w, unsigned flags, uint64_t *pos, uint64_t *val,
+                   size_t out_cap, uint64_t *count);
+
 /* ---- device utilities for benches and large-size verification ----------------- */
 /* Counter-based uniform {A,C,G,T} (resp. {A,C,G,T,N}, P(N)=1/16) generator,
  * identical to oracle/cnt_oracle.c's, so a host can regenerate any chunk.

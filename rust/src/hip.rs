@@ -66,6 +66,9 @@ extern "C" {
     fn cnt_validate(n: *const u8, n_len: usize, flags: c_uint, invalid: *mut u64) -> c_int;
     fn cnt_kmers_dev(d_bits: *const c_void, len: usize, k: c_uint, flags: c_uint, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
     fn cnt_kmers(bits: *const u64, len: usize, k: c_uint, flags: c_uint, out: *mut u64, out_cap: usize) -> c_int;
+    fn cnt_minimizers_work_bytes(len: usize, k: c_uint, w: c_uint, bytes: *mut usize) -> c_int;
+    fn cnt_minimizers_dev(d_bits: *const c_void, len: usize, k: c_uint, w: c_uint, flags: c_uint, d_pos: *mut c_void, d_val: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_minimizers(bits: *const u64, len: usize, k: c_uint, w: c_uint, flags: c_uint, pos: *mut u64, val: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -446,6 +449,40 @@ pub fn kmers_hip(bits: &[u64], len: usize, k: u32, canonical: bool) -> Vec<u64> 
     res
 }
 
+/// The (w,k)-minimizers (`1 <= k <= 32`, `1 <= w <= 256`): in each window of `w` consecutive k-mers the position with the
+/// smallest `(fmix64(k-mer), position)`, each distinct position once, ascending; returns the positions and their k-mers
+/// (forward, or canonical as in `kmers_hip`).  No window (`len < k + w - 1`): two empty vectors.
+pub fn minimizers_hip(bits: &[u64], len: usize, k: u32, w: u32, canonical: bool) -> (Vec<u64>, Vec<u64>) {
+    need(bits, len);
+    if k == 0 || k > 32 {
+        panic!("k must be in 1..32");
+    }
+    if w == 0 || w > 256 {
+        panic!("w must be in 1..256");
+    }
+    let m = if len >= k as usize { len - k as usize + 1 } else { 0 };
+    let windows = if m >= w as usize { m - w as usize + 1 } else { 0 };
+    // a random sequence selects about 2/(w+1) of its windows; a longer result is fetched again at its reported size
+    let mut cap = std::cmp::min(windows, 2 * windows / (w as usize + 1) + windows / 16 + 64);
+    let mut pos: Vec<u64> = Vec::with_capacity(cap);
+    let mut val: Vec<u64> = Vec::with_capacity(cap);
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    let mut n: u64 = 0;
+    unsafe {
+        let fits = cnt_minimizers(bits.as_ptr(), len, k, w, flags, pos.as_mut_ptr(), val.as_mut_ptr(), cap, &mut n) == 0;
+        if !fits {
+            // CNT_ECAP left the count in n; any other status comes back from the second call and panics in check
+            cap = n as usize;
+            pos = Vec::with_capacity(cap);
+            val = Vec::with_capacity(cap);
+            check(cnt_minimizers(bits.as_ptr(), len, k, w, flags, pos.as_mut_ptr(), val.as_mut_ptr(), cap, &mut n));
+        }
+        pos.set_len(n as usize);
+        val.set_len(n as usize);
+    }
+    (pos, val)
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -536,6 +573,32 @@ pub fn kmers_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, canonical: bool,
     }
     let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
     unsafe { check(cnt_kmers_dev(d_bits.ptr, len, k, flags, d_out.ptr, d_out.bytes / 8, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `minimizers_hip_dev` needs for this call (0 when there is no window).
+pub fn minimizers_work_bytes(len: usize, k: u32, w: u32) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_minimizers_work_bytes(len, k, w, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the minimizers of `len` device-resident nucleotides (see `minimizers_hip`): `d_count` (one u64) is SET to their
+/// number n, the first min(n, capacity) positions go to `d_pos` and, when given, their k-mers to `d_val`; `d_work` holds at
+/// least `minimizers_work_bytes` bytes of any contents.
+pub fn minimizers_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, w: u32, canonical: bool, d_pos: &DeviceBuffer, d_val: Option<&DeviceBuffer>, d_count: &DeviceBuffer, d_work: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    let cap = match d_val {
+        Some(v) => std::cmp::min(d_pos.bytes, v.bytes) / 8,
+        None => d_pos.bytes / 8,
+    };
+    let val_ptr = match d_val {
+        Some(v) => v.ptr,
+        None => std::ptr::null_mut(),
+    };
+    unsafe { check(cnt_minimizers_dev(d_bits.ptr, len, k, w, flags, d_pos.ptr, val_ptr, cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
