@@ -7,13 +7,19 @@ device-resident 16 GiB ASCII buffer (-> 4 GiB packed) followed by bits_to_n deco
 packed words (-> 16 GiB ASCII).  Inputs are generated on the device (counter-based ACGT
 generator, seed in the JSON) and are resident in HBM before the timed region starts.
 
-    python bench.py [--steps K --warmup W]                              (N=1)
+    python bench.py [--steps K --warmup W] [--full]                     (N=1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          (N>1, one rank per GPU: the driver's form)
     python bench.py --gpus N --steps K --warmup W                       (N>1 WITHOUT a launcher: ONE process drives the
         N devices through the enqueue-only sharded tier -- cnt_*_sharded_dev_enqueue queues all K steps on one library
-        stream per shard, ONE cnt_sharded_dev_wait; no process group at all -- and prints the same JSON line plus
-        `scaling_overhead_us`; what north_star describes; bench/bench_single_process.py)
+        stream per shard, ONE cnt_sharded_dev_wait; no process group at all -- and prints the same JSON line, with --full
+        plus `scaling_overhead_us`; what north_star describes; bench/bench_single_process.py)
+
+A plain run does what the headline needs and no more, in every form: it generates the input, warms up, times the K steps,
+checks the timed buffers (below; --no-verify skips that), writes --dump-outputs and prints the line.  --full adds, after the
+timed region, everything that takes runs of its own: the fused pass, the configs blocks, configs[4]'s shard, the same-run
+ceilings, the live HBM traffic, the 5-letter codec and packed-domain ops, the host tier, the CPU baseline and, without a
+launcher at N > 1, the scaling overhead.  None of it changes `value` or `ms_per_step`.
 
 N>1: the global buffer (N x per-GPU size) is cut into contiguous chunks on word boundaries,
 rank r owns chunk r (cute_nucleotides_amd/sharding.py); there is no data-path collective --
@@ -21,7 +27,7 @@ the process group (gloo over loopback by default, RCCL with CNT_BENCH_BACKEND=nc
 for the barrier and the max-over-ranks of the timing.  Weak scaling: per-GPU work is fixed.
 
 The per-GPU size stays 2^34 nt (the metric's 16 GiB) at every N, so the driver's N = 1, 2, 4, 8 values form a
-weak-scaling curve; BASELINE.json configs[4] (256 GiB over 8 GPUs = 2^35 nt per GPU) is measured in the same run
+weak-scaling curve; BASELINE.json configs[4] (256 GiB over 8 GPUs = 2^35 nt per GPU) is measured in the same --full run
 as `configs4_shard` (encode of a 2^35-nt shard on every rank, per-GPU and aggregate Gnt/s).  `ranks` lists every
 rank's device (index, PCI address, UUID, NUMA node, visible-device count) and its own kernel times, so an N-GPU
 line shows N distinct devices and no data-path collective.
@@ -31,9 +37,9 @@ ranks (N encoded + N decoded per step and rank), inputs already in HBM.  `roofli
 the n_to_bits encode kernel (the north-star target), `roofline_decode` for bits_to_n; both
 use ALGORITHMIC bytes (1.25 B/nt: encode 1 read + 0.25 written, decode 0.25 read + 1
 written) over the kernel's average duration measured live with HIP events on the
-launch stream; `roofline.traffic` = HBM bytes per launch measured by this run itself (two child `rocprofv3 --pmc`
-passes, FETCH_SIZE and WRITE_SIZE separately, calibrated on known-size probes; falls back to the committed
-profiles/hbm_traffic.json, and says so in `traffic_source`).  `cpu_baseline` times the oracle's ports of the reference's fastest AVX2
+launch stream; `roofline.traffic` = HBM bytes per launch, with --full measured by this run itself (two child `rocprofv3 --pmc`
+passes, FETCH_SIZE and WRITE_SIZE separately, calibrated on known-size probes), otherwise, or if that
+fails, quoted from the committed profiles/hbm_traffic.json; `traffic_source` says which.  With --full, `cpu_baseline` times the oracle's ports of the reference's fastest AVX2
 paths (n_to_bits_movemask / bits_to_n_shuffle) on this box's host cores: rank 0, at EVERY N (north_star: "next to the
 reference's own AVX2/BMI2 path timed on the GPU box's host cores in the same run", at 1, 2, 4 and 8 GPUs), after all GPU work of
 the line -- the host threads never compete with a rank that is still enqueueing.  At N > 1 the reference-faithful
@@ -69,11 +75,15 @@ def parse_args():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--log2-nt", type=int, default=34, help="per-GPU nucleotides = 2^k (default 34 = 16 GiB, the metric size)")
     p.add_argument("--seed", type=lambda s: int(s, 0), default=0x5EED)
-    p.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU-baseline time budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline: the fused pass, the configs blocks, the ceilings, the live HBM "
+                        "traffic, the 5-letter codec and packed-domain ops, the host tier, the CPU baseline and, at N > 1 without a "
+                        "launcher, the scaling overhead (without it: set up, warm up, time the steps, verify, dump, print)")
+    p.add_argument("--cpu-seconds", type=float, default=16.0, help="with --full: CPU-baseline time budget (0 = skip)")
     p.add_argument("--no-verify", action="store_true")
-    p.add_argument("--no-extras", action="store_true", help="headline only: skip the ceilings, the configs block and the fused pass")
-    p.add_argument("--no-live-traffic", action="store_true", help="do not spawn the two rocprofv3 --pmc child runs; quote profiles/hbm_traffic.json")
-    p.add_argument("--shard-log2-nt", type=int, default=35, help="per-GPU shard of BASELINE.json configs[4] (256 GiB over 8 GPUs = 2^35 nt each)")
+    p.add_argument("--no-extras", action="store_true", help="with --full: skip all it adds but the CPU baseline and the scaling overhead")
+    p.add_argument("--no-live-traffic", action="store_true", help="with --full: do not spawn the two rocprofv3 --pmc child runs; quote profiles/hbm_traffic.json")
+    p.add_argument("--shard-log2-nt", type=int, default=35, help="with --full: per-GPU shard of BASELINE.json configs[4] (256 GiB over 8 GPUs = 2^35 nt each)")
     p.add_argument("--dump-outputs", metavar="DIR", nargs="?", const=os.path.join(ROOT, "bench_outputs"),
                    help="after the timed steps, write a seeded sample of what the last one computed to DIR/*.npy, 64 MB at most over "
                         "all shards (bench/bench_measure.py dump_outputs); without DIR: bench_outputs/ in the repository, ignored by git")
@@ -405,7 +415,7 @@ def main():
         del kat, kat_bits
         verified = ok
 
-    extras = not args.no_extras
+    extras = args.full and not args.no_extras
     # ---- BASELINE.json configs[3] in passing: the FUSED round trip over the same buffers -------------------
     fused = None
     if extras:
@@ -635,7 +645,7 @@ def main():
                 "per_gpu_read_view_frac": {"min": round(min(gbs(s["nt"], s["encode_ms"]["median"]) for s in sh) / HBM_PEAK_GBS, 4),
                                            "max": round(max(gbs(s["nt"], s["encode_ms"]["median"]) for s in sh) / HBM_PEAK_GBS, 4)},
             }
-        if args.cpu_seconds > 0:  # every N (north_star: the CPU path timed in the same run at 1, 2, 4 and 8 GPUs); all GPU work is done
+        if args.full and args.cpu_seconds > 0:  # every N (north_star: the CPU path timed in the same run at 1, 2, 4 and 8 GPUs); all GPU work is done
             line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, faithful_tables=world == 1)
             if world > 1:
                 line["cpu_baseline"]["when"] = "after the timed region and every extra of all %d ranks (they wait at the final barrier)" % world

@@ -8,7 +8,7 @@ direction) never reaches a device, because the host is a whole queue ahead.  No 
 staging: north_star's "shards trivially by contiguous chunk across the 8 GPUs of one node" (word w depends on nucleotides
 [32w, 32w+32) only, n_to_bits.rs:38-43 -- nothing needs a barrier).
 
-`scaling_overhead_us` on the line: what driving N devices from one thread costs PER STEP that driving one does not --
+`scaling_overhead_us` on a --full line: what driving N devices from one thread costs PER STEP that driving one does not --
 (wall per step of the N-shard run) - ceil(N / visible devices) x (wall per step of the SAME K steps queued for shard 0
 alone through a one-shard queue, same process, measured right after).  On N real devices the factor is 1 and the number
 is the exposed overhead of the fan-out; with shards folded onto fewer devices (test hook) the folded shards share one
@@ -137,14 +137,25 @@ def main_single_process(args, cpu_baseline=None):
         for k in range(N):
             dump_outputs(args.dump_outputs, torch, d_pk[k], d_out[k], lens_l[k], args.seed, parts[k][0] // 32, N, "shard%d_" % k)
 
-    # the same K steps for shard 0 alone, through a one-shard queue: what one device costs without the fan-out
-    q1 = open_queue(1)
-    one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
-    b_in, b_pk, b_out, b_len, b_words = one(d_in[0]), one(d_pk[0]), one(d_out[0]), sizes(lens_l[:1], 1), sizes(words_l[:1], 1)
-    run_steps(q1, max(1, args.warmup), b_in, b_len, b_pk, b_words, b_out, 1)
-    elapsed_one = run_steps(q1, args.steps, b_in, b_len, b_pk, b_words, b_out, 1)[0]
-    _lib.check(L.cnt_sharded_dev_close(q1))
-    scaling_overhead_us = (elapsed - per_dev * elapsed_one) / args.steps * 1e6
+    # --full: the same K steps for shard 0 alone, through a one-shard queue: what one device costs without the fan-out
+    scaling = None
+    if args.full:
+        q1 = open_queue(1)
+        one = lambda t: (ctypes.c_void_p * 1)(t.data_ptr())
+        b_in, b_pk, b_out, b_len, b_words = one(d_in[0]), one(d_pk[0]), one(d_out[0]), sizes(lens_l[:1], 1), sizes(words_l[:1], 1)
+        run_steps(q1, max(1, args.warmup), b_in, b_len, b_pk, b_words, b_out, 1)
+        elapsed_one = run_steps(q1, args.steps, b_in, b_len, b_pk, b_words, b_out, 1)[0]
+        _lib.check(L.cnt_sharded_dev_close(q1))
+        del b_in, b_pk, b_out
+        scaling_overhead_us = (elapsed - per_dev * elapsed_one) / args.steps * 1e6
+        scaling = {
+            "per_step_us": round(scaling_overhead_us, 2), "share_of_step": round(scaling_overhead_us * 1e-6 / (elapsed / args.steps), 5),
+            "host_enqueue_us_per_step": round(host_s / args.steps * 1e6, 2),
+            "wall_ms_per_step_all_shards": round(elapsed / args.steps * 1e3, 4), "wall_ms_per_step_shard0_alone": round(elapsed_one / args.steps * 1e3, 4),
+            "shards_per_device": per_dev,
+            "definition": "wall per step over all N shards - shards_per_device x wall per step of the same K steps queued for shard 0 alone "
+                          "(one-shard queue, same process): what the fan-out from one thread costs a step; host_enqueue_us_per_step is host "
+                          "time inside the enqueue calls, hidden while it is below the device time per step"}
 
     verified = None
     if not args.no_verify:
@@ -162,8 +173,9 @@ def main_single_process(args, cpu_baseline=None):
         del kat, kat_bits
 
     # ---- BASELINE.json configs[3] in passing: the FUSED round trip of every shard through the same queue (not part of value) ----
+    extras = args.full and not args.no_extras
     fused_rows, ceilings = None, None
-    if not args.no_extras:
+    if extras:
         sums = [devutil.checksum_words(t) for t in d_pk] if verified is not None else None
         reps = 5
         for _ in range(reps + 1):  # one warm-up op + five timed ones, queued back to back, one wait
@@ -191,12 +203,12 @@ def main_single_process(args, cpu_baseline=None):
             ceilings = {"error": "bench/libcnt_probes.so not built (run __graft_entry__.build())" if P is None else "size not probe-able"}
 
     # ---- BASELINE.json configs[4]: 2^35 nt per GPU through the same queue ------------------------------------------------
-    del d_out, d_pk, d_in, a_in, a_pk, a_out, b_in, b_pk, b_out
+    del d_out, d_pk, d_in, a_in, a_pk, a_out
     for i in range(min(N, visible)):
         with torch.cuda.device(i):
             torch.cuda.empty_cache()
     shard_rows, shard_wall = [None] * N, None
-    if not args.no_extras and args.shard_log2_nt > 0:
+    if extras and args.shard_log2_nt > 0:
         s_len = 1 << args.shard_log2_nt
         fits = all(torch.cuda.mem_get_info(i)[0] > per_dev * 2.3 * s_len + (4 << 30) for i in range(min(N, visible)))
         if fits:
@@ -257,7 +269,7 @@ def main_single_process(args, cpu_baseline=None):
         with torch.cuda.device(i):
             torch.cuda.empty_cache()
     # HBM bytes per launch for roofline.traffic: live on device 0 (every buffer of this process is free), else the committed N = 1 figure, labelled
-    traffic, traffic_source, live = traffic_for_line(args.log2_nt, N, not args.no_extras and not args.no_live_traffic, child_device=0)
+    traffic, traffic_source, live = traffic_for_line(args.log2_nt, N, extras and not args.no_live_traffic, child_device=0)
 
     nt_per_step = 2 * n_global
     value = nt_per_step * args.steps / elapsed / 1e9
@@ -290,15 +302,6 @@ def main_single_process(args, cpu_baseline=None):
             "encode_kernel": dict(devutil.variants("encode"))[devutil.get_tuning("encode")],
             "decode_kernel": dict(devutil.variants("decode"))[devutil.get_tuning("decode")],
         },
-        "scaling_overhead_us": round(scaling_overhead_us, 2),
-        "scaling_overhead": {
-            "per_step_us": round(scaling_overhead_us, 2), "share_of_step": round(scaling_overhead_us * 1e-6 / (elapsed / args.steps), 5),
-            "host_enqueue_us_per_step": round(host_s / args.steps * 1e6, 2),
-            "wall_ms_per_step_all_shards": round(elapsed / args.steps * 1e3, 4), "wall_ms_per_step_shard0_alone": round(elapsed_one / args.steps * 1e3, 4),
-            "shards_per_device": per_dev,
-            "definition": "wall per step over all N shards - shards_per_device x wall per step of the same K steps queued for shard 0 alone "
-                          "(one-shard queue, same process): what the fan-out from one thread costs a step; host_enqueue_us_per_step is host "
-                          "time inside the enqueue calls, hidden while it is below the device time per step"},
         "encode_gnts_per_gpu": round(lens_l[0] / (enc_ms0 * 1e-3) / 1e9, 3), "decode_gnts_per_gpu": round(lens_l[0] / (dec_ms0 * 1e-3) / 1e9, 3),
         "encode_gnts_all_gpus": round(n_global / (enc_slow * 1e-3) / 1e9, 3), "decode_gnts_all_gpus": round(n_global / (dec_slow * 1e-3) / 1e9, 3),
         "hbm_read_roofline_frac_encode_per_gpu": round(n_per / (enc_slow * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
@@ -315,6 +318,8 @@ def main_single_process(args, cpu_baseline=None):
                             "device (nt_per_step = 2 x n_gpus x nt_per_gpu); wall clock around the K queued steps and the one wait, "
                             "device-synchronised on both sides",
     }
+    if scaling is not None:
+        line["scaling_overhead_us"], line["scaling_overhead"] = scaling["per_step_us"], scaling
     sh = [r["configs4_shard"] for r in rows if r.get("configs4_shard") and "encode_ms" in r["configs4_shard"]]
     if sh:
         tot = sum(x["nt"] for x in sh)
@@ -353,8 +358,9 @@ def main_single_process(args, cpu_baseline=None):
             line["ceilings"]["encode_vs"] = {"of_read4_write1_ceiling": round(e_gbs / ceilings["read4_write1_encode_shape"]["GBs"], 4),
                                              "read_only_view_of_read_only_ceiling": round(gbs(lens_l[0], enc_ms0) / ceilings["read_only"]["GBs"], 4)}
             line["ceilings"]["decode_vs"] = {"of_read1_write4_ceiling": round(d_gbs / ceilings["read1_write4_decode_shape"]["GBs"], 4)}
-    line["codec5"] = line["packed_ops"] = {"on": "the N = 1 line (SURVEY 8 f-1 / f-4 at the metric size; per-GPU work does not change with N)"}
-    if cpu_baseline is not None and args.cpu_seconds > 0:
+    if args.full:
+        line["codec5"] = line["packed_ops"] = {"on": "the N = 1 line (SURVEY 8 f-1 / f-4 at the metric size; per-GPU work does not change with N)"}
+    if cpu_baseline is not None and args.full and args.cpu_seconds > 0:
         # north_star: the reference's AVX2 path timed on this box's host cores IN THE SAME RUN, at every N; after all GPU work
         # of the line, so its threads never compete with the thread that enqueues for N devices
         line["cpu_baseline"] = cpu_baseline(args.cpu_seconds, faithful_tables=False)

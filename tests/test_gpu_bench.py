@@ -7,6 +7,7 @@ import os
 import socket
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -21,7 +22,7 @@ def _last_json(text):
 
 
 def test_single_gpu_line_small():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--log2-nt", "30",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "3", "--warmup", "1", "--log2-nt", "30",
                           "--shard-log2-nt", "31", "--cpu-seconds", "0", "--no-live-traffic"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json(out.stdout)
@@ -110,6 +111,31 @@ def test_dump_outputs_are_the_timed_steps_results(oracle, tmp_path):
     assert len(np.load(tmp_path / "words_index.npy")) == 1 << 18
 
 
+FULL_ONLY = ("fused_round_trip", "configs", "ceilings", "configs4_sharded_encode", "codec5", "packed_ops", "host_tier", "cpu_baseline",
+             "scaling_overhead_us", "scaling_overhead")
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_run_is_the_headline_alone(gpus, oracle, tmp_path):
+    """without --full a run sets up, warms up, times the steps, checks the timed buffers, writes --dump-outputs and prints the
+    line -- nothing that takes runs of its own (no extra block, no CPU leg, no counter-collection child: the traffic is the
+    committed figure or none), in the N = 1 form and in the one-process N > 1 form, and little time beside the steps"""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "2", "--log2-nt", "26",
+           "--dump-outputs", str(tmp_path)]
+    t0 = time.perf_counter()
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=dict(os.environ, CNT_BENCH_SHARE_GPU="1"))
+    wall = time.perf_counter() - t0
+    assert out.returncode == 0, out.stderr[-3000:]
+    j = _last_json(out.stdout)
+    assert j["n_gpus"] == gpus and j["steps"] == 5 and j["warmup"] == 2 and j["verified"] is True
+    assert j["unit"] == "Gnt/s" and j["higher_is_better"] is True and j["dtype"] == "u8" and j["ms_per_step"] > 0
+    assert abs(j["value"] - j["config"]["nt_per_step"] * j["steps"] / (j["ms_per_step"] * 1e-3 * j["steps"]) / 1e9) < 0.01 * j["value"]
+    assert [k for k in FULL_ONLY if k in j] == [] and j["traffic_live"] is None and j["roofline"]["traffic"] is None
+    assert all(r["configs4_shard"] is None and r["fused_ms_median"] is None and r["encode_ms"]["n"] == 5 for r in j["ranks"])
+    assert wall - (j["steps"] + j["warmup"]) * j["ms_per_step"] * 1e-3 < 30.0, wall
+    _check_dump(tmp_path, gpus, 1 << 26, oracle)
+
+
 @pytest.mark.parametrize("n", [4, 8])
 def test_single_process_form_folded_onto_one_gpu(n, oracle, tmp_path):
     """ONE process over N devices through the enqueue-only sharded tier, with N = 4 and 8 shards folded onto
@@ -122,7 +148,7 @@ def test_single_process_form_folded_onto_one_gpu(n, oracle, tmp_path):
     # N = 8) and a non-null, labelled `roofline.traffic`
     cpu_single = "1" if n == 4 else "0"
     # one process, N shards, everything queued, one wait (100 steps: the overhead figure multiplies a one-shard wall time by N)
-    single = ["--gpus", str(n), "--steps", "100", "--warmup", "5", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_single,
+    single = ["--full", "--gpus", str(n), "--steps", "100", "--warmup", "5", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_single,
               "--dump-outputs", str(tmp_path)]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + single, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -159,7 +185,7 @@ def test_rank_form_folded_onto_one_gpu(cpu_leg, oracle, tmp_path):
         port = s.getsockname()[1]
     env = dict(os.environ, CNT_BENCH_SHARE_GPU="1")
     ranks, cpu_ranks = 3, "1" if cpu_leg else "0"
-    common = ["--gpus", str(ranks), "--steps", "20", "--warmup", "2", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_ranks,
+    common = ["--full", "--gpus", str(ranks), "--steps", "20", "--warmup", "2", "--log2-nt", "26", "--shard-log2-nt", "27", "--cpu-seconds", cpu_ranks,
               "--dump-outputs", str(tmp_path)]
     # `ranks` ranks sharing cuda:0 over gloo, barrier + max over ranks
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(ranks), "--master-addr", "127.0.0.1",
@@ -203,7 +229,7 @@ def test_two_rank_launch_path_shares_one_gpu():
         port = s.getsockname()[1]
     env = dict(os.environ, CNT_BENCH_SHARE_GPU="1")  # default control-plane backend (gloo)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--log2-nt", "28", "--shard-log2-nt", "29", "--cpu-seconds", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -235,7 +261,7 @@ def test_gpus_n_without_a_launcher_is_one_process_over_n_devices():
     launch").  It now drives the N devices from ONE process through the enqueue-only sharded tier (cnt_*_sharded_dev_enqueue,
     one cnt_sharded_dev_wait for all steps) and prints the same JSON line.  On the 1-GPU box the N shards are folded onto cuda:0 (CNT_BENCH_SHARE_GPU=1 ->
     cnt_test_alias_devices); without that the shortage of devices is a clear error, not a wrong run."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2-nt", "28", "--shard-log2-nt", "29"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2-nt", "28", "--shard-log2-nt", "29"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=dict(os.environ, CNT_BENCH_SHARE_GPU="1"))
     assert out.returncode == 0, out.stderr[-3000:]
     j = _last_json(out.stdout)
@@ -312,7 +338,7 @@ def test_cpu_baseline_and_host_tier_blocks():
     """the N = 1 line's CPU leg: the port timed on this box's cores (threads, logical and physical cores stated
     separately), the reference-faithful allocation-inclusive rows incl. the 5-letter functions and the 1 MiB / 1 GiB
     sizes, and the host-tier crossover table against one CPU thread"""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--log2-nt", "28",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--log2-nt", "28",
                           "--shard-log2-nt", "28", "--cpu-seconds", "2"], capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     j = _last_json(out.stdout)
