@@ -8,39 +8,48 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib
+from ._lib import CNT_KMER_CANONICAL, check, lib
 from .n_to_bits import _counter, _dev_guard, _enqueue, _out_words, _p, _u8, _u64
 
 CNT_ALLOW_N = 0x2
-CNT_KMER_CANONICAL = 0x10
 
 
-def _need(bits, length):
+def _packed(bits, length):
+    """the host tier's packed input: a contiguous uint64 array holding `length` nucleotides"""
+    bits = _u64(bits)
     if length > bits.size * 32:
         raise ValueError("The length is greater than the number of nucleotides!")
+    return bits
+
+
+def _packed_dev(bits, length):
+    """the device tier's packed input: a contiguous int64 CUDA tensor holding `length` nucleotides; returns torch"""
+    torch = _dev_guard(bits)
+    if bits.dtype != torch.int64:
+        raise TypeError("packed words must be an int64 tensor")
+    if length > bits.numel() * 32:
+        raise ValueError("The length is greater than the number of nucleotides!")
+    return torch
 
 
 # ---- host tier --------------------------------------------------------------------------
 def hamming_hip(a, b, length):
-    a, b = _u64(a), _u64(b)
-    _need(a, length)
-    _need(b, length)
+    a, b = _u64(a), _u64(b)  # both types are checked before either length
+    a, b = _packed(a, length), _packed(b, length)
     out = ctypes.c_uint64(0)
     check(lib().cnt_hamming(_p(a), _p(b), length, ctypes.byref(out)))
     return out.value
 
 
 def complement_hip(bits, length):
-    bits = _u64(bits)
-    _need(bits, length)
+    bits = _packed(bits, length)
     out = np.empty(lib().cnt_words_for(length), dtype=np.uint64)
     check(lib().cnt_complement(_p(bits), length, _p(out)))
     return out
 
 
 def reverse_complement_hip(bits, length):
-    bits = _u64(bits)
-    _need(bits, length)
+    bits = _packed(bits, length)
     out = np.empty(lib().cnt_words_for(length), dtype=np.uint64)
     check(lib().cnt_reverse_complement(_p(bits), length, _p(out)))
     return out
@@ -56,8 +65,7 @@ def kmers_hip(bits, length, k, canonical=False, out=None):
     """The length-k+1 k-mers of the sequence as np.uint64 (include/cute_nt.h "k-mers"): k-mer i packed like a sequence of
     length k, or with canonical=True the smaller of it and its reverse complement as u64.  `out` (optional, >= m uint64, e.g.
     from pinned_empty) receives them; the [:m] view is returned."""
-    bits = _u64(bits)
-    _need(bits, length)
+    bits = _packed(bits, length)
     m = _n_kmers(length, k)
     if out is None:
         out = np.empty(m, dtype=np.uint64)
@@ -79,8 +87,7 @@ def minimizers_hip(bits, length, k, w, canonical=False, values=True):
     position with the smallest (fmix64(k-mer), position), each distinct position once, ascending.  Returns numpy uint64
     (pos, val) of length n, val the k-mers at pos (forward, or canonical with canonical=True), or None with values=False.
     The output buffers start at a guess of n and are sized to the reported n once if the guess was short."""
-    bits = _u64(bits)
-    _need(bits, length)
+    bits = _packed(bits, length)
     n_win = _n_windows(length, k, w)
     cap = min(n_win, 2 * n_win // (w + 1) + n_win // 16 + 64)  # a random sequence selects ~2/(w+1) of its windows
     flags = CNT_KMER_CANONICAL if canonical else 0
@@ -120,11 +127,7 @@ def hamming_dev(a, b, length, acc=None):
 
 
 def _unary_dev(fn, bits, length, out):
-    torch = _dev_guard(bits)
-    if bits.dtype != torch.int64:
-        raise TypeError("packed words must be an int64 tensor")
-    if length > bits.numel() * 32:
-        raise ValueError("The length is greater than the number of nucleotides!")
+    torch = _packed_dev(bits, length)
     words = lib().cnt_words_for(length)
     out = _out_words(torch, out, words, bits)
     _enqueue(bits, fn, ctypes.c_void_p(bits.data_ptr()), length, ctypes.c_void_p(out.data_ptr()))
@@ -142,11 +145,7 @@ def reverse_complement_dev(bits, length, out=None):
 def kmers_dev(bits, length, k, canonical=False, out=None):
     """Device tier of kmers_hip: `bits` an int64 CUDA tensor, the result the [:m] view of an int64 tensor (`out` if given)
     enqueued on torch's current stream."""
-    torch = _dev_guard(bits)
-    if bits.dtype != torch.int64:
-        raise TypeError("packed words must be an int64 tensor")
-    if length > bits.numel() * 32:
-        raise ValueError("The length is greater than the number of nucleotides!")
+    torch = _packed_dev(bits, length)
     m = _n_kmers(length, k)
     out = _out_words(torch, out, m, bits)
     _enqueue(bits, lib().cnt_kmers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
@@ -167,11 +166,7 @@ def minimizers_dev(bits, length, k, w, canonical=False, values=True, pos=None, v
     stream has run (val is None with values=False).  Without `pos` / `val` they hold W = m-w+1 entries, the most n can be;
     given ones of any capacity receive the first min(n, capacity) entries.  `work` (>= minimizers_work_bytes bytes, any
     contents) and `count` may be reused across calls, e.g. in a captured graph."""
-    torch = _dev_guard(bits)
-    if bits.dtype != torch.int64:
-        raise TypeError("packed words must be an int64 tensor")
-    if length > bits.numel() * 32:
-        raise ValueError("The length is greater than the number of nucleotides!")
+    torch = _packed_dev(bits, length)
     n_win = _n_windows(length, k, w)
     # a given pos / val may hold fewer than W entries (the first min(n, capacity) are written); val at least as many as pos
     pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(n_win, 1), dtype=torch.int64, device=bits.device)

@@ -14,8 +14,11 @@
 //   device_tier.inc     alignment plan + kernel selection: encode_dev, decode_dev, round_trip_dev, *2_dev
 //   host_tier.inc       zero-copy small calls, pinned-staging pipeline over a ring of 3 (2..4) slots
 //   sharded_tier.inc    partition, NUMA-pinned worker pool, resident-shard runner
-//   (this file)         tuning knobs and every exported symbol of include/cute_nt.h
-//   packed_ops_abi.inc  the packed-domain operations' entry points
+//   (this file)         tuning knobs, the launch helpers and host_call (the packed-domain host tier), every exported
+//                       symbol of include/cute_nt.h but those of the packed-domain operations:
+//   packed_ops_abi.inc  hamming, complement, reverse complement, validate
+//   kmer_abi.inc        k-mers
+//   minimizer_abi.inc   (w,k)-minimizers
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>
@@ -133,15 +136,93 @@ constexpr bool tune_decode_window() { return true; }
 inline uint64_t decode_cache_nt() { return chip_info().cache_nt; }
 #endif
 
-inline unsigned generic_grid(uint64_t items) {
-    uint64_t b = (items + kBlock - 1) / kBlock;
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>(b, 1), 1u << 16);
+// the grid of a grid-stride kernel over `items` items: one per thread, at least one and at most 2^16 workgroups
+inline unsigned generic_grid(uint64_t items, unsigned block = kBlock) {
+    return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + block - 1) / block, 1), 1u << 16);
+}
+
+// n_tiles one-workgroup tiles of `block` threads in launches of at most max_tiles_per_launch(block): launch(first, n) for each
+template <typename F>
+void split_launches(uint64_t n_tiles, int block, F&& launch) {
+    const uint64_t per_launch = max_tiles_per_launch(block);
+    for (uint64_t first = 0; first < n_tiles; first += per_launch) launch(first, std::min(per_launch, n_tiles - first));
+}
+
+// the end of a synchronous call on stream s: drains it whatever rc is, and reports rc, else the drain's own status
+int finish(hipStream_t s, int rc) {
+    const int r2 = hip_rc(hipStreamSynchronize(s));
+    return rc != CNT_OK ? rc : r2;
 }
 
 #include "shim_host_ctx.inc"
 #include "device_tier.inc"
 #include "host_tier.inc"
 #include "sharded_tier.inc"
+
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc) ----------------
+// A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
+// is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
+enum class Dir { in, out, counted };
+struct HostBuf {
+    const void* p;  // NULL: absent, no view
+    size_t bytes;
+    Dir dir;
+};
+
+// dev(d, aux, s) enqueues a _dev entry point on the views d[i] of the buffers b[i]; host_call runs it on the calling thread's
+// stream[0] and returns when the stream has drained:
+//   - every present buffer pinned with a device view, and no written one overlapping another (an in-place call): on those
+//     views, the kernels read and write the caller's memory over the link (include/cute_nt.h "pinned caller memory");
+//   - otherwise ALL of them staged, one whole-buffer transfer each way through the thread's grow-only device scratch
+//     (DevCtx::d_aux, freed by cnt_shutdown): b[0] in d_aux[0], the others back to back in d_aux[1].
+// aux is d_aux[2], aux_bytes of it in either lane (the codec's checked host tier keeps its counters there too, host_tier.inc).
+// With a `result`, aux's first word ends in *result, and starts from 0 when `zero` (a count the call adds to).  Every exit after
+// the first enqueue goes through finish(): no copy can still read or write the caller's pageable memory after the return (the
+// retire() rule of host_tier.inc).
+template <size_t N, typename F>
+int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool zero, F&& dev) {
+    DevCtx* c = nullptr;
+    CNT_TRY(t_ctx.get(&c));
+    CNT_TRY(c->ensure_streams());
+    void* d[N] = {};
+    bool staged = false;
+    for (size_t i = 0; i < N && !staged; ++i) {
+        if (!b[i].p) continue;
+        for (size_t j = 0; j < i; ++j)
+            staged = staged || (b[j].p && (b[i].dir != Dir::in || b[j].dir != Dir::in) && overlaps(b[i].p, b[i].bytes, b[j].p, b[j].bytes));
+        staged = staged || !host_range_is_pinned(b[i].p, b[i].bytes, &d[i]) || !d[i];
+    }
+    if (staged) {
+        size_t at[N] = {}, tail = 0;
+        for (size_t i = 1; i < N; ++i)
+            if (b[i].p) {
+                at[i] = tail;
+                tail += (b[i].bytes + 7) & ~(size_t)7;
+            }
+        CNT_TRY(c->ensure_aux(0, b[0].bytes));
+        if (N > 1) CNT_TRY(c->ensure_aux(1, std::max<size_t>(tail, 1)));  // an empty buffer still gets an address
+        for (size_t i = 0; i < N; ++i) d[i] = b[i].p ? static_cast<uint8_t*>(c->d_aux[i ? 1 : 0]) + at[i] : nullptr;
+    }
+    if (aux_bytes) CNT_TRY(c->ensure_aux(2, aux_bytes));
+    hipStream_t s = c->stream[0];
+    int rc = CNT_OK;
+    for (size_t i = 0; i < N; ++i)
+        if (staged && b[i].p && b[i].dir == Dir::in && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(d[i], b[i].p, b[i].bytes, hipMemcpyHostToDevice, s));
+    if (rc == CNT_OK && result && zero) rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
+    if (rc == CNT_OK) rc = dev(d, c->d_aux[2], s);
+    for (size_t i = 0; i < N; ++i)
+        if (staged && b[i].p && b[i].dir == Dir::out && rc == CNT_OK)
+            rc = hip_rc(hipMemcpyAsync(const_cast<void*>(b[i].p), d[i], b[i].bytes, hipMemcpyDeviceToHost, s));
+    if (rc == CNT_OK && result) rc = hip_rc(hipMemcpyAsync(result, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
+    CNT_TRY(finish(s, rc));
+    bool copying = false;  // the `counted` outputs, now that *result is known
+    for (size_t i = 0; i < N; ++i) {
+        const size_t got = staged && b[i].p && b[i].dir == Dir::counted ? std::min<uint64_t>(*result, b[i].bytes / 8) * 8 : 0;
+        if (got && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(const_cast<void*>(b[i].p), d[i], got, hipMemcpyDeviceToHost, s));
+        copying = copying || got;
+    }
+    return copying ? finish(s, rc) : CNT_OK;
+}
 
 }  // namespace
 

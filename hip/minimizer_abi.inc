@@ -1,7 +1,7 @@
 // minimizer_abi.inc -- C-ABI entry points of (w,k)-minimizer sampling (include/cute_nt.h, "k-mers"): the scratch query
 // cnt_minimizers_work_bytes, cnt_minimizers_dev (enqueue-only on a caller stream: three kernels, no allocation, no
-// synchronisation, capturable in a graph) and cnt_minimizers (host tier: staged through DevCtx::d_aux, or in place when the
-// caller's input and outputs are pinned).  Included at the end of cute_nt.hip, after kmer_abi.inc.
+// synchronisation, capturable in a graph) and cnt_minimizers (host tier: cute_nt.hip's host_call, staged through DevCtx::d_aux,
+// or in place when the caller's input and outputs are pinned).  Included at the end of cute_nt.hip.
 #include "minimizer_kernels.hpp"
 
 namespace {
@@ -59,14 +59,15 @@ int cnt_minimizers_dev(const void* d_bits, size_t len, unsigned k, unsigned w, u
     uint64_t* val = static_cast<uint64_t*>(d_val);
     uint64_t* count = static_cast<uint64_t*>(d_count);
     const uint32_t canonical = (flags & CNT_KMER_CANONICAL) ? 1u : 0u;
-    const uint64_t per_launch = max_tiles_per_launch(kMinBlock);
-    for (uint64_t t = 0; t < n_tiles; t += per_launch)
-        hipLaunchKernelGGL((minimizer_tiles<false>), dim3((unsigned)std::min(per_launch, n_tiles - t)), dim3(kMinBlock), 0, s, in,
-                           (uint64_t)len, (uint32_t)k, (uint32_t)w, canonical, t, counts, offs, pos, val, (uint64_t)out_cap);
+    split_launches(n_tiles, kMinBlock, [&](uint64_t t, uint64_t n) {
+        hipLaunchKernelGGL((minimizer_tiles<false>), dim3((unsigned)n), dim3(kMinBlock), 0, s, in, (uint64_t)len, (uint32_t)k, (uint32_t)w,
+                           canonical, t, counts, offs, pos, val, (uint64_t)out_cap);
+    });
     hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);
-    for (uint64_t t = 0; t < n_tiles; t += per_launch)
-        hipLaunchKernelGGL((minimizer_tiles<true>), dim3((unsigned)std::min(per_launch, n_tiles - t)), dim3(kMinBlock), 0, s, in,
-                           (uint64_t)len, (uint32_t)k, (uint32_t)w, canonical, t, counts, offs, pos, val, (uint64_t)out_cap);
+    split_launches(n_tiles, kMinBlock, [&](uint64_t t, uint64_t n) {
+        hipLaunchKernelGGL((minimizer_tiles<true>), dim3((unsigned)n), dim3(kMinBlock), 0, s, in, (uint64_t)len, (uint32_t)k, (uint32_t)w,
+                           canonical, t, counts, offs, pos, val, (uint64_t)out_cap);
+    });
     return hip_rc(hipGetLastError());
 }
 
@@ -78,37 +79,13 @@ int cnt_minimizers(const uint64_t* bits, size_t len, unsigned k, unsigned w, uns
         if (count) *count = 0;
         return CNT_OK;
     }
-    const size_t in_bytes = cnt_words_for(len) * 8, cap = std::min<uint64_t>(n_win, out_cap), out_bytes = cap * 8;
-    const size_t work_bytes = minimizer_work_bytes(n_win);
-    DevCtx* c = nullptr;
-    CNT_TRY(t_ctx.get(&c));
-    CNT_TRY(c->ensure_aux(2, 8 + work_bytes));  // the device count, then the scratch
-    uint8_t* aux2 = static_cast<uint8_t*>(c->d_aux[2]);
+    // the pinned lane needs cap > 0: an empty pos is never pinned
+    const size_t cap = std::min<uint64_t>(n_win, out_cap), work_bytes = minimizer_work_bytes(n_win);
     uint64_t n = 0;
-    void *dbits = nullptr, *dpos = nullptr, *dval = nullptr;
-    if (cap && host_range_is_pinned(bits, in_bytes, &dbits) && host_range_is_pinned(pos, out_bytes, &dpos) && dbits && dpos &&
-        (!val || (host_range_is_pinned(val, out_bytes, &dval) && dval))) {
-        hipStream_t s = c->stream[0];  // pinned in, pinned out: three kernels over the link
-        int rc = cnt_minimizers_dev(dbits, len, k, w, flags, dpos, dval, out_cap, aux2, aux2 + 8, work_bytes, s);
-        if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(&n, aux2, 8, hipMemcpyDeviceToHost, s));
-        CNT_TRY(finish(s, rc));
-    } else {
-        CNT_TRY(c->ensure_aux(0, in_bytes));
-        CNT_TRY(c->ensure_aux(1, std::max<size_t>(out_bytes * (val ? 2 : 1), 8)));
-        hipStream_t s = c->stream[0];
-        uint64_t* dp = static_cast<uint64_t*>(c->d_aux[1]);
-        uint64_t* dv = val ? dp + cap : nullptr;
-        int rc = hip_rc(hipMemcpyAsync(c->d_aux[0], bits, in_bytes, hipMemcpyHostToDevice, s));
-        if (rc == CNT_OK) rc = cnt_minimizers_dev(c->d_aux[0], len, k, w, flags, dp, dv, cap, aux2, aux2 + 8, work_bytes, s);
-        if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(&n, aux2, 8, hipMemcpyDeviceToHost, s));
-        CNT_TRY(finish(s, rc));
-        const size_t got = std::min<uint64_t>(n, cap) * 8;
-        if (got) {
-            rc = hip_rc(hipMemcpyAsync(pos, dp, got, hipMemcpyDeviceToHost, s));
-            if (rc == CNT_OK && val) rc = hip_rc(hipMemcpyAsync(val, dv, got, hipMemcpyDeviceToHost, s));
-            CNT_TRY(finish(s, rc));
-        }
-    }
+    CNT_TRY(host_call({{bits, cnt_words_for(len) * 8, Dir::in}, {pos, cap * 8, Dir::counted}, {val, cap * 8, Dir::counted}}, 8 + work_bytes, &n,
+                      false, [&](void* const* d, void* aux, hipStream_t s) {  // aux: the device count, then the scratch
+                          return cnt_minimizers_dev(d[0], len, k, w, flags, d[1], d[2], cap, aux, static_cast<uint8_t*>(aux) + 8, work_bytes, s);
+                      }));
     *count = n;
     return n > out_cap ? CNT_ECAP : CNT_OK;
 }

@@ -2,19 +2,10 @@
 // "packed-domain operations"): Hamming distance, complement, reverse complement on 2-bit packed
 // words, and alphabet validation of ASCII buffers.  Included at the end of cute_nt.hip (one
 // translation unit: the kernel headers define non-template __global__ functions).  Device tier
-// = enqueue-only on a caller stream; host tier = whole-buffer H2D / kernel / D2H through per-thread
+// = enqueue-only on a caller stream; host tier = cute_nt.hip's host_call: whole-buffer H2D / kernel / D2H through per-thread
 // grow-only device scratch (convenience entry points, not chunked / not tuned for PCIe) -- or, when the caller's slices
 // are pinned, the same kernels reading and writing them over the link.
 #include "packed_ops_kernels.hpp"
-
-namespace {
-
-inline unsigned capped_grid(uint64_t items, unsigned block) {
-    return (unsigned)std::min<uint64_t>(std::max<uint64_t>((items + block - 1) / block, 1), 1u << 16);
-}
-
-
-}  // namespace
 
 extern "C" {
 
@@ -69,16 +60,14 @@ int cnt_hamming_dev(const void* d_a, const void* d_b, size_t len, void* d_count,
             n_tiles = 0;
         }
         if (n_tiles) {
-            const uint64_t per_launch = max_tiles_per_launch(kRedBlock);
-            for (uint64_t first = 0; first < n_tiles; first += per_launch) {
-                const uint64_t n = std::min(per_launch, n_tiles - first);
+            split_launches(n_tiles, kRedBlock, [&](uint64_t first, uint64_t n) {
                 const uint8_t* pa8 = static_cast<const uint8_t*>(d_a) + (head_words + first * kTileWords) * 8;
                 const uint8_t* pb8 = static_cast<const uint8_t*>(d_b) + (head_words + first * kTileWords) * 8;
                 if (g_reduce_xi.load(std::memory_order_relaxed))
                     hipLaunchKernelGGL((hamming_tiles<U, true>), dim3((unsigned)n), dim3(kRedBlock), 0, s, pa8, pb8, n, partial + first, xcd_shift());
                 else
                     hipLaunchKernelGGL((hamming_tiles<U, false>), dim3((unsigned)n), dim3(kRedBlock), 0, s, pa8, pb8, n, partial + first, xcd_shift());
-            }
+            });
             hipLaunchKernelGGL(sum_partials, dim3(sum_partials_grid(n_tiles)), dim3(kRedBlock), 0, s, partial, n_tiles, count);
             const int rc = hip_rc(hipGetLastError());
             HIP_TRY(hipFreeAsync(partial, s));
@@ -94,7 +83,7 @@ int cnt_hamming_dev(const void* d_a, const void* d_b, size_t len, void* d_count,
     }
     done_words = tile_words ? head_words + tile_words : 0;
     if (done_words < words) {
-        hipLaunchKernelGGL(hamming_generic, dim3(capped_grid(words - done_words, kRedBlock)), dim3(kRedBlock), 0, s,
+        hipLaunchKernelGGL(hamming_generic, dim3(generic_grid(words - done_words, kRedBlock)), dim3(kRedBlock), 0, s,
                            static_cast<const uint64_t*>(d_a), static_cast<const uint64_t*>(d_b), (uint64_t)len, done_words, words, count);
         HIP_TRY(hipGetLastError());
     }
@@ -115,13 +104,11 @@ int cnt_complement_dev(const void* d_bits, size_t len, void* d_out, void* stream
     if (head_words > (len >> 5)) head_words = 0;
     if (((pi + 8 * head_words) & 15) == 0 && ((po + 8 * head_words) & 15) == 0) {
         const uint64_t n_tiles = ((len >> 5) - head_words) / kTileWords;
-        const uint64_t per_launch = max_tiles_per_launch(B);
-        for (uint64_t first = 0; first < n_tiles; first += per_launch) {
-            const uint64_t n = std::min(per_launch, n_tiles - first);
+        split_launches(n_tiles, B, [&](uint64_t first, uint64_t n) {
             hipLaunchKernelGGL((complement_tiles<B, U>), dim3((unsigned)n), dim3(B), 0, s,
                                static_cast<const uint8_t*>(d_bits) + (head_words + first * kTileWords) * 8,
                                static_cast<uint8_t*>(d_out) + (head_words + first * kTileWords) * 8, n);
-        }
+        });
         if (n_tiles && head_words)
             hipLaunchKernelGGL(complement_generic, dim3(1), dim3(kBlock), 0, s, static_cast<const uint64_t*>(d_bits),
                                static_cast<uint64_t*>(d_out), (uint64_t)(32 * head_words), (uint64_t)0, head_words);
@@ -129,7 +116,7 @@ int cnt_complement_dev(const void* d_bits, size_t len, void* d_out, void* stream
         done_words = n_tiles ? head_words + n_tiles * kTileWords : 0;
     }
     if (done_words < words) {
-        hipLaunchKernelGGL(complement_generic, dim3(capped_grid(words - done_words, kBlock)), dim3(kBlock), 0, s,
+        hipLaunchKernelGGL(complement_generic, dim3(generic_grid(words - done_words)), dim3(kBlock), 0, s,
                            static_cast<const uint64_t*>(d_bits), static_cast<uint64_t*>(d_out), (uint64_t)len, done_words, words);
         HIP_TRY(hipGetLastError());
     }
@@ -149,16 +136,14 @@ int cnt_reverse_complement_dev(const void* d_bits, size_t len, void* d_out, void
     uint64_t head = ((128 - (reinterpret_cast<uintptr_t>(d_out) & 127)) & 127) >> 3;
     if (head > (len >> 5)) head = 0;
     const uint64_t n_tiles = ((len >> 5) - head) / kTileWords;  // every window of these tiles lies inside the input
-    const uint64_t per_launch = max_tiles_per_launch(B);
-    for (uint64_t first = 0; first < n_tiles; first += per_launch) {
-        const uint64_t n = std::min(per_launch, n_tiles - first);
+    split_launches(n_tiles, B, [&](uint64_t first, uint64_t n) {
         const uint64_t skip = head + first * kTileWords;  // output words in front of this launch
         hipLaunchKernelGGL((reverse_complement_tiles<B>), dim3((unsigned)n), dim3(B), 0, s, static_cast<const uint8_t*>(d_bits),
                            static_cast<uint8_t*>(d_out) + skip * 8, (uint64_t)len - 32 * skip, n);
-    }
+    });
     auto word_kernel = [&](uint64_t first_word, uint64_t end_word) {
         if (first_word < end_word)
-            hipLaunchKernelGGL(reverse_complement_words, dim3(capped_grid(end_word - first_word, kBlock)), dim3(kBlock), 0, s,
+            hipLaunchKernelGGL(reverse_complement_words, dim3(generic_grid(end_word - first_word)), dim3(kBlock), 0, s,
                                static_cast<const uint64_t*>(d_bits), static_cast<uint64_t*>(d_out), (uint64_t)len, first_word, end_word);
     };
     if (n_tiles) {
@@ -215,16 +200,14 @@ int cnt_validate_dev(const void* d_n, size_t n_len, unsigned flags, void* d_inva
             n_tiles = 0;
         }
         if (n_tiles) {
-            const uint64_t per_launch = max_tiles_per_launch(kRedBlock);
             const uint8_t* p = n + head;
-            for (uint64_t first = 0; first < n_tiles; first += per_launch) {
-                const uint64_t m = std::min(per_launch, n_tiles - first);
+            split_launches(n_tiles, kRedBlock, [&](uint64_t first, uint64_t m) {
                 const bool xi = g_reduce_xi.load(std::memory_order_relaxed) != 0;
                 if (allow_n && xi) hipLaunchKernelGGL((validate_tiles<U, true, true>), dim3((unsigned)m), dim3(kRedBlock), 0, s, p + first * kTile, m, partial + first, xcd_shift());
                 else if (allow_n) hipLaunchKernelGGL((validate_tiles<U, true, false>), dim3((unsigned)m), dim3(kRedBlock), 0, s, p + first * kTile, m, partial + first, xcd_shift());
                 else if (xi) hipLaunchKernelGGL((validate_tiles<U, false, true>), dim3((unsigned)m), dim3(kRedBlock), 0, s, p + first * kTile, m, partial + first, xcd_shift());
                 else hipLaunchKernelGGL((validate_tiles<U, false, false>), dim3((unsigned)m), dim3(kRedBlock), 0, s, p + first * kTile, m, partial + first, xcd_shift());
-            }
+            });
             hipLaunchKernelGGL(sum_partials, dim3(sum_partials_grid(n_tiles)), dim3(kRedBlock), 0, s, partial, n_tiles, count);
             if (head) {
                 if (allow_n) hipLaunchKernelGGL((validate_generic<true>), dim3(1), dim3(kRedBlock), 0, s, n, (uint64_t)0, head, count);
@@ -238,7 +221,7 @@ int cnt_validate_dev(const void* d_n, size_t n_len, unsigned flags, void* d_inva
     }
 #endif
     if (done < n_len) {
-        const unsigned g = capped_grid(n_len - done, kRedBlock);
+        const unsigned g = generic_grid(n_len - done, kRedBlock);
         if (allow_n) hipLaunchKernelGGL((validate_generic<true>), dim3(g), dim3(kRedBlock), 0, s, n, done, (uint64_t)n_len, count);
         else hipLaunchKernelGGL((validate_generic<false>), dim3(g), dim3(kRedBlock), 0, s, n, done, (uint64_t)n_len, count);
         HIP_TRY(hipGetLastError());
@@ -246,68 +229,23 @@ int cnt_validate_dev(const void* d_n, size_t n_len, unsigned flags, void* d_inva
     return CNT_OK;
 }
 
-// ---- host tier -------------------------------------------------------------------------
-// Whole-buffer H2D / kernel / D2H on the calling thread's own stream, through the same grow-only per-thread
-// device scratch idea the codec's host tier uses (DevCtx::d_aux: device-only, no hipMalloc per call, freed by cnt_shutdown).  Convenience entry points: one transfer
-// each way, not chunked.
-// Every exit after the first enqueue goes through finish(): the stream is ALWAYS drained before the function
-// returns, so no hipMemcpyAsync can still be reading the caller's pageable input or writing the caller's output
-// (the retire() rule of host_tier.inc).
-static int finish(hipStream_t s, int rc) {
-    const int r2 = hip_rc(hipStreamSynchronize(s));
-    return rc != CNT_OK ? rc : r2;
-}
-
+// ---- host tier: host_call (cute_nt.hip) ---------------------------------------------------
 int cnt_hamming(const uint64_t* a, const uint64_t* b, size_t len, uint64_t* distance) {
     if (!distance) return CNT_EINVAL;
     *distance = 0;
     if (len == 0) return CNT_OK;
     if (!a || !b) return CNT_EINVAL;
     const size_t bytes = cnt_words_for(len) * 8;
-    DevCtx* c = nullptr;
-    CNT_TRY(t_ctx.get(&c));
-    void *da = nullptr, *db = nullptr;
-    if (host_range_is_pinned(a, bytes, &da) && host_range_is_pinned(b, bytes, &db) && da && db) {
-        // both sequences in pinned memory (include/cute_nt.h "pinned caller memory"): the kernel reads them over the link, no copies
-        CNT_TRY(c->ensure_aux(2, 16));
-        hipStream_t s = c->stream[0];
-        int rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
-        if (rc == CNT_OK) rc = cnt_hamming_dev(da, db, len, c->d_aux[2], s);
-        if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(distance, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
-        return finish(s, rc);
-    }
-    CNT_TRY(c->ensure_aux(0, bytes));  // the two sequences and the counter
-    CNT_TRY(c->ensure_aux(1, bytes));
-    CNT_TRY(c->ensure_aux(2, 16));
-    hipStream_t s = c->stream[0];
-    int rc = hip_rc(hipMemcpyAsync(c->d_aux[0], a, bytes, hipMemcpyHostToDevice, s));
-    if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(c->d_aux[1], b, bytes, hipMemcpyHostToDevice, s));
-    if (rc == CNT_OK) rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
-    if (rc == CNT_OK) rc = cnt_hamming_dev(c->d_aux[0], c->d_aux[1], len, c->d_aux[2], s);
-    if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(distance, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
-    return finish(s, rc);
+    return host_call({{a, bytes, Dir::in}, {b, bytes, Dir::in}}, 16, distance, true,
+                     [&](void* const* d, void* count, hipStream_t s) { return cnt_hamming_dev(d[0], d[1], len, count, s); });
 }
 
 static int host_unary(const uint64_t* bits, size_t len, uint64_t* out, int (*fn)(const void*, size_t, void*, void*)) {
     if (len == 0) return CNT_OK;
     if (!bits || !out) return CNT_EINVAL;
     const size_t bytes = cnt_words_for(len) * 8;
-    DevCtx* c = nullptr;
-    CNT_TRY(t_ctx.get(&c));
-    void *dbits = nullptr, *dout = nullptr;
-    // (an `out` that overlaps `bits` keeps going through the device scratch, where in-place has always worked)
-    if (!overlaps(bits, bytes, out, bytes) && host_range_is_pinned(bits, bytes, &dbits) && host_range_is_pinned(out, bytes, &dout) && dbits && dout) {
-        CNT_TRY(c->ensure_streams());
-        hipStream_t s = c->stream[0];
-        return finish(s, fn(dbits, len, dout, s));  // pinned in, pinned out: one kernel over the link
-    }
-    CNT_TRY(c->ensure_aux(0, bytes));
-    CNT_TRY(c->ensure_aux(1, bytes));
-    hipStream_t s = c->stream[0];
-    int rc = hip_rc(hipMemcpyAsync(c->d_aux[0], bits, bytes, hipMemcpyHostToDevice, s));
-    if (rc == CNT_OK) rc = fn(c->d_aux[0], len, c->d_aux[1], s);
-    if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(out, c->d_aux[1], bytes, hipMemcpyDeviceToHost, s));
-    return finish(s, rc);
+    return host_call({{bits, bytes, Dir::in}, {out, bytes, Dir::out}}, 0, nullptr, false,
+                     [&](void* const* d, void*, hipStream_t s) { return fn(d[0], len, d[1], s); });
 }
 
 int cnt_complement(const uint64_t* bits, size_t len, uint64_t* out) { return host_unary(bits, len, out, cnt_complement_dev); }
@@ -321,25 +259,8 @@ int cnt_validate(const uint8_t* n, size_t n_len, unsigned flags, uint64_t* inval
     if (flags & ~CNT_ALLOW_N) return CNT_EINVAL;
     if (n_len == 0) return CNT_OK;
     if (!n) return CNT_EINVAL;
-    DevCtx* c = nullptr;
-    CNT_TRY(t_ctx.get(&c));
-    void* dn = nullptr;
-    if (host_range_is_pinned(n, n_len, &dn) && dn) {  // pinned letters: counted where they lie
-        CNT_TRY(c->ensure_aux(2, 16));
-        hipStream_t s = c->stream[0];
-        int rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
-        if (rc == CNT_OK) rc = cnt_validate_dev(dn, n_len, flags, c->d_aux[2], s);
-        if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(invalid, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
-        return finish(s, rc);
-    }
-    CNT_TRY(c->ensure_aux(0, n_len));
-    CNT_TRY(c->ensure_aux(2, 16));
-    hipStream_t s = c->stream[0];
-    int rc = hip_rc(hipMemcpyAsync(c->d_aux[0], n, n_len, hipMemcpyHostToDevice, s));
-    if (rc == CNT_OK) rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
-    if (rc == CNT_OK) rc = cnt_validate_dev(c->d_aux[0], n_len, flags, c->d_aux[2], s);
-    if (rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(invalid, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
-    return finish(s, rc);
+    return host_call({{n, n_len, Dir::in}}, 16, invalid, true,
+                     [&](void* const* d, void* count, hipStream_t s) { return cnt_validate_dev(d[0], n_len, flags, count, s); });
 }
 
 }  // extern "C"

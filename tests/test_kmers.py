@@ -286,15 +286,25 @@ def kmer_plan(out_ptr, n_len, k, launch_tiles=KMER_HW_LAUNCH_TILES):
     return head, tiles, tail, -(-tiles // launch_tiles) + (head > 0) + (tail > 0)
 
 
-def test_kmer_plan_matches_the_launcher_source():
+def assert_split_launches_by_max_tiles_per_launch():
+    """cute_nt.hip's split_launches, which the launchers call with their block: launches of max_tiles_per_launch(block) tiles"""
+    shim = open(os.path.join(ROOT, "hip", "cute_nt.hip")).read()
+    for line in ("void split_launches(uint64_t n_tiles, int block, F&& launch) {",
+                 "const uint64_t per_launch = max_tiles_per_launch(block);",
+                 "for (uint64_t first = 0; first < n_tiles; first += per_launch) launch(first, std::min(per_launch, n_tiles - first));"):
+        assert line in shim, line
+
+
+def test_kmer_plan_matches_the_launcher_and_splitter_source():
     """the constants kmer_plan restates are the ones in the sources"""
     src = open(os.path.join(ROOT, "hip", "kmer_kernels.hpp")).read()
     assert "constexpr int kKmerBlock = 256, kKmerU = 2;" in src and "(uint64_t)kKmerBlock * 2 * kKmerU" in src
     abi = open(os.path.join(ROOT, "hip", "kmer_abi.inc")).read()
     for line in ("uint64_t head = ((128 - (reinterpret_cast<uintptr_t>(d_out) & 127)) & 127) >> 3;",
                  "const uint64_t tile_end = std::min<uint64_t>(m, 32 * (words - 1));",
-                 "const uint64_t per_launch = max_tiles_per_launch(kKmerBlock);"):
+                 "split_launches(n_tiles, kKmerBlock, [&](uint64_t t, uint64_t n) {"):
         assert line in abi, line
+    assert_split_launches_by_max_tiles_per_launch()
     assert KMER_HW_LAUNCH_TILES == 8388544
     # the 2^33 case of test_gpu_kmers_full_size_in_two_launches: heads 0 and 13, two tile launches each
     n_len = (1 << 33) + 4133

@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from test_gpu_multi_launch import launch_tiles  # noqa: F401 -- the fixture: the lab build at 64 / 128 tiles per launch
+from test_kmers import assert_split_launches_by_max_tiles_per_launch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COMP = bytes.maketrans(b"ACGT", b"TGCA")
@@ -379,16 +380,19 @@ def minimizer_plan(n_len, k, w, launch_tiles=MIN_HW_LAUNCH_TILES):
     return tiles, (2 * -(-tiles // launch_tiles) + 1) if tiles else 0
 
 
-def test_minimizer_plan_matches_the_launcher_source():
+def test_minimizer_plan_matches_the_launcher_and_splitter_source():
     src = open(os.path.join(ROOT, "hip", "minimizer_kernels.hpp")).read()
     assert "constexpr int kMinBlock = 256;" in src and "constexpr uint32_t kMinTile = 2048, kMinMaxW = 256;" in src
     abi = open(os.path.join(ROOT, "hip", "minimizer_abi.inc")).read()
-    for line in ("const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;",
-                 "const uint64_t per_launch = max_tiles_per_launch(kMinBlock);",
-                 "hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);",
+    scan = "hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);"
+    for line in ("const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;", scan,
                  "if (n_win == 0) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;"):
         assert line in abi, line
-    assert abi.count("for (uint64_t t = 0; t < n_tiles; t += per_launch)") == 2
+    # the two tile passes, each in launches of max_tiles_per_launch(kMinBlock) tiles, with the one scan launch between them
+    tiles = "split_launches(n_tiles, kMinBlock, [&](uint64_t t, uint64_t n) {"
+    assert abi.count(tiles) == 2 and abi.count("minimizer_scan") == 1
+    assert abi.index(tiles) < abi.index(scan) < abi.rindex(tiles)
+    assert_split_launches_by_max_tiles_per_launch()
     assert MIN_HW_LAUNCH_TILES == 8388544
     assert minimizer_plan((1 << 32) + 33, 21, 11) == (2097153, 3)
     assert minimizer_plan(64 * TILE * 3 + 30, 21, 11, 64) == (192, 7) and minimizer_plan(64 * TILE * 3 + 31, 21, 11, 64) == (193, 9)
