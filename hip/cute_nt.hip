@@ -204,24 +204,39 @@ int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool ze
         for (size_t i = 0; i < N; ++i) d[i] = b[i].p ? static_cast<uint8_t*>(c->d_aux[i ? 1 : 0]) + at[i] : nullptr;
     }
     if (aux_bytes) CNT_TRY(c->ensure_aux(2, aux_bytes));
+    // a staged buffer that starts in pinned memory and leaves it cannot be handed to hipMemcpyAsync (host_range_leaves_pinned):
+    // it travels through an ordinary copy of itself, h[i]
+    std::vector<uint8_t> bounce[N];
+    void* h[N] = {};
+    for (size_t i = 0; i < N; ++i) {
+        if (staged && b[i].p && host_range_leaves_pinned(b[i].p, b[i].bytes)) {
+            bounce[i].resize(b[i].bytes);
+            if (b[i].dir == Dir::in) memcpy(bounce[i].data(), b[i].p, b[i].bytes);
+        }
+        h[i] = bounce[i].empty() ? const_cast<void*>(b[i].p) : bounce[i].data();
+    }
     hipStream_t s = c->stream[0];
     int rc = CNT_OK;
     for (size_t i = 0; i < N; ++i)
-        if (staged && b[i].p && b[i].dir == Dir::in && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(d[i], b[i].p, b[i].bytes, hipMemcpyHostToDevice, s));
+        if (staged && b[i].p && b[i].dir == Dir::in && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(d[i], h[i], b[i].bytes, hipMemcpyHostToDevice, s));
     if (rc == CNT_OK && result && zero) rc = hip_rc(hipMemsetAsync(c->d_aux[2], 0, 8, s));
     if (rc == CNT_OK) rc = dev(d, c->d_aux[2], s);
     for (size_t i = 0; i < N; ++i)
         if (staged && b[i].p && b[i].dir == Dir::out && rc == CNT_OK)
-            rc = hip_rc(hipMemcpyAsync(const_cast<void*>(b[i].p), d[i], b[i].bytes, hipMemcpyDeviceToHost, s));
+            rc = hip_rc(hipMemcpyAsync(h[i], d[i], b[i].bytes, hipMemcpyDeviceToHost, s));
     if (rc == CNT_OK && result) rc = hip_rc(hipMemcpyAsync(result, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
     CNT_TRY(finish(s, rc));
-    bool copying = false;  // the `counted` outputs, now that *result is known
+    size_t got[N] = {};  // the `counted` outputs, now that *result is known
+    bool copying = false;
     for (size_t i = 0; i < N; ++i) {
-        const size_t got = staged && b[i].p && b[i].dir == Dir::counted ? std::min<uint64_t>(*result, b[i].bytes / 8) * 8 : 0;
-        if (got && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(const_cast<void*>(b[i].p), d[i], got, hipMemcpyDeviceToHost, s));
-        copying = copying || got;
+        got[i] = staged && b[i].p && b[i].dir == Dir::counted ? std::min<uint64_t>(*result, b[i].bytes / 8) * 8 : 0;
+        if (got[i] && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(h[i], d[i], got[i], hipMemcpyDeviceToHost, s));
+        copying = copying || got[i];
     }
-    return copying ? finish(s, rc) : CNT_OK;
+    if (copying) CNT_TRY(finish(s, rc));
+    for (size_t i = 0; i < N; ++i)
+        if (!bounce[i].empty() && b[i].dir != Dir::in) memcpy(const_cast<void*>(b[i].p), bounce[i].data(), b[i].dir == Dir::out ? b[i].bytes : got[i]);
+    return CNT_OK;
 }
 
 }  // namespace

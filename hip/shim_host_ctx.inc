@@ -181,9 +181,13 @@ inline int host_slots() {
 
 // Is [p, p + bytes) pinned host memory the copy engines can use in place -- hipHostMalloc'ed (cnt_host_alloc, a torch tensor
 // with pin_memory=True ...) or hipHostRegister'ed (cnt_host_register)?  Then the host tier skips its staging copy on that side
-// (host_tier.inc): the DMA reads / writes the caller's buffer itself.  One or two runtime queries (~1 us); ordinary memory makes
-// the first one fail, which is the answer.  The range must lie inside ONE allocation where the runtime can say (hipHostMalloc);
-// for registered memory it cannot, and both ends are asked instead.  CNT_HOST_PINNED=0: never look, always stage.
+// (host_tier.inc): the DMA reads / writes the caller's buffer itself.  Two or three runtime queries (~1 us); ordinary memory
+// makes the first one fail, which is the answer.  The range must lie inside ONE allocation or ONE registration: a range that
+// runs from one registration into the next (adjacent or not), over an unregistered hole or out of pinned memory is staged,
+// whatever its two ends are.  hipMemGetAddressRange gives a hipHostMalloc'ed allocation's base and size; for registered memory
+// it gives the registration's size but no base (ROCm 7.2), and HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, asked at p, supplies the
+// registration's first byte (the same answer at every byte of it; devicePointer is p's own device address, not the
+// registration's).  No answer from either: staged.  CNT_HOST_PINNED=0: never look, always stage.
 inline bool host_pinned_enabled() {
     static const bool v = [] {
         const char* e = getenv("CNT_HOST_PINNED");
@@ -198,8 +202,8 @@ inline bool pinned_host_byte(const void* p, hipPointerAttribute_t* a) {
     }
     return a->type == hipMemoryTypeHost;
 }
-inline bool host_range_is_pinned(const void* p, size_t bytes, void** device_view = nullptr /* how a kernel addresses p */) {
-    if (!p || !bytes || !host_pinned_enabled()) return false;
+inline bool host_range_in_one_pinned(const void* p, size_t bytes, void** device_view) {
+    if (!p || !bytes) return false;
     hipPointerAttribute_t a;
     if (!pinned_host_byte(p, &a)) return false;
     if (device_view) *device_view = a.devicePointer;
@@ -211,9 +215,29 @@ inline bool host_range_is_pinned(const void* p, size_t bytes, void** device_view
         const uintptr_t lo = reinterpret_cast<uintptr_t>(dp), end = reinterpret_cast<uintptr_t>(base) + size;
         return lo + bytes >= lo && lo + bytes <= end;
     }
-    if (ranged != hipSuccess) (void)hipGetLastError();
-    hipPointerAttribute_t b;  // registered in place: the runtime reports a size but no base (ROCm 7.2) -- ask the last byte too
-    return pinned_host_byte(static_cast<const uint8_t*>(p) + bytes - 1, &b);
+    if (ranged != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    // registered in place: the registration that holds p starts at `start` (asked with p: an address of p's space) and is
+    // `size` bytes long; the range must end inside it
+    void* start = nullptr;
+    if (hipPointerGetAttribute(&start, HIP_POINTER_ATTRIBUTE_RANGE_START_ADDR, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p), first = reinterpret_cast<uintptr_t>(start);
+    return start && size && first <= lo && lo - first <= size && bytes <= size - (lo - first);
+}
+inline bool host_range_is_pinned(const void* p, size_t bytes, void** device_view = nullptr /* how a kernel addresses p */) {
+    return host_pinned_enabled() && host_range_in_one_pinned(p, bytes, device_view);
+}
+// Does [p, p + bytes) start in pinned memory and leave it (into ordinary memory, another registration, past a hole)?  The
+// runtime then refuses a hipMemcpy* of the range (hipErrorInvalidValue, ROCm 7.2: it holds the copy to the allocation or
+// registration of its first byte), so a staged copy of it has to go through ordinary memory (host_call's bounce buffers).
+inline bool host_range_leaves_pinned(const void* p, size_t bytes) {
+    hipPointerAttribute_t a;
+    return p && bytes && pinned_host_byte(p, &a) && !host_range_in_one_pinned(p, bytes, nullptr);
 }
 
 struct DevCtx {

@@ -131,7 +131,9 @@ int cnt_host_tier_info(int *device, int *numa_node, int *helper_cpus, int *stagi
  * run as ONE kernel that reads and writes the caller's buffers over the link -- no host copy, no copy engine (2^20 nt: 36 us
  * instead of 64).  "Pinned" is asked of the runtime at every call (~1 us) -- hipHostMalloc'ed by anyone (cnt_host_alloc below,
  * a torch tensor with pin_memory=True, hipHostMalloc in the caller's own code) or registered in place (cnt_host_register,
- * hipHostRegister); the library keeps no table, so memory freed or unregistered later is simply staged again.  The reference's
+ * hipHostRegister); the library keeps no table, so memory freed or unregistered later is simply staged again.  A slice counts as
+ * pinned only when ONE allocation or ONE registration covers all of it: a slice that runs across two registrations (adjacent or
+ * with a hole between them), or from pinned into ordinary memory, is staged like ordinary memory.  The reference's
  * signature (&[u8] -> Vec<u64>) allocates per call and cannot use this; the `_into` forms of the mirrors with buffers from
  * cnt_host_alloc can (rust/src/hip.rs PinnedBuf, cute_nucleotides.hpp PinnedBuffer, cute_nucleotides_amd.pinned_empty).
  * The packed-domain host entry points (cnt_hamming, cnt_complement, cnt_reverse_complement, cnt_validate, cnt_kmers,
