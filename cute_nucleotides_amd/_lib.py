@@ -109,6 +109,8 @@ SIGNATURES = {
     "cnt_validate": (_int, [_vp, _sz, _uint, ctypes.POINTER(_u64)]),
     "cnt_kmers_dev": (_int, [_vp, _sz, _uint, _uint, _vp, _sz, _vp]),
     "cnt_kmers": (_int, [_vp, _sz, _uint, _uint, _vp, _sz]),
+    "cnt_kmer_counts_dev": (_int, [_vp, _sz, _uint, _uint, _vp, _sz, _vp]),
+    "cnt_kmer_counts": (_int, [_vp, _sz, _uint, _uint, _vp, _sz]),
     "cnt_minimizers_work_bytes": (_int, [_sz, _uint, _uint, ctypes.POINTER(_sz)]),
     "cnt_minimizers_dev": (_int, [_vp, _sz, _uint, _uint, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "cnt_minimizers": (_int, [_vp, _sz, _uint, _uint, _uint, _vp, _vp, _sz, _vp]),

@@ -1,5 +1,6 @@
 """Operations on 2-bit packed nucleotides without decoding: Hamming distance,
-complement, reverse complement, k-mer extraction (forward and canonical), (w,k)-minimizers, and alphabet validation of ASCII buffers.  The reference does
+complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
+(w,k)-minimizers, and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -73,6 +74,25 @@ def kmers_hip(bits, length, k, canonical=False, out=None):
         raise ValueError("out must be a contiguous uint64 array with >= %d elements" % m)
     check(lib().cnt_kmers(_p(bits), length, k, CNT_KMER_CANONICAL if canonical else 0, _p(out), out.size))
     return out[:m]
+
+
+KMER_COUNTS_MAX_K = 12
+
+
+def _n_bins(k):
+    if not 1 <= k <= KMER_COUNTS_MAX_K:
+        raise ValueError("k must be in 1..%d" % KMER_COUNTS_MAX_K)
+    return 4 ** k
+
+
+def kmer_counts_hip(bits, length, k, canonical=False):
+    """The k-mer spectrum of the sequence as np.uint64[4**k] (include/cute_nt.h "k-mer counts"): entry v is the number of
+    k-mers whose kmers_hip value (same `canonical`) is v; 1 <= k <= 12.  k = 1 is base composition in code order A, C, T, G."""
+    bins = _n_bins(k)
+    bits = _packed(bits, length)
+    out = np.empty(bins, dtype=np.uint64)
+    check(lib().cnt_kmer_counts(_p(bits), length, k, CNT_KMER_CANONICAL if canonical else 0, _p(out), out.size))
+    return out
 
 
 def _n_windows(length, k, w):
@@ -151,6 +171,18 @@ def kmers_dev(bits, length, k, canonical=False, out=None):
     _enqueue(bits, lib().cnt_kmers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
              ctypes.c_void_p(out.data_ptr()), out.numel())
     return out[:m]
+
+
+def kmer_counts_dev(bits, length, k, canonical=False, out=None):
+    """Device tier of kmer_counts_hip, enqueued on torch's current stream: returns the [:4**k] view of an int64 CUDA tensor.
+    A given `out` (contiguous int64, on the input's device, >= 4**k entries) is ADDED TO -- count several sequences or chunks
+    into one spectrum -- and its entries past 4**k are left alone; without one a zeroed table is allocated."""
+    bins = _n_bins(k)
+    torch = _packed_dev(bits, length)
+    out = torch.zeros(bins, dtype=torch.int64, device=bits.device) if out is None else _out_words(torch, out, bins, bits)
+    _enqueue(bits, lib().cnt_kmer_counts_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
+             ctypes.c_void_p(out.data_ptr()), out.numel())
+    return out[:bins]
 
 
 def minimizers_work_bytes(length, k, w):

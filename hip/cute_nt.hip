@@ -19,6 +19,7 @@
 //   packed_ops_abi.inc  hamming, complement, reverse complement, validate
 //   kmer_abi.inc        k-mers
 //   minimizer_abi.inc   (w,k)-minimizers
+//   kmer_count_abi.inc  k-mer counts
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>
@@ -113,6 +114,8 @@ std::atomic<int> g_decode_rot{-1};  // further 4-KiB output pages peeled in fron
 inline int tune_decode_rot() { return g_decode_rot.load(std::memory_order_relaxed); }
 std::atomic<int> g_decode_window{1};  // 1 (shipped): bits_to_n_window for calls past the Infinity Cache whose packed stream is off its lines or dwords; 0: round 4's stream / shifted kernels
 inline bool tune_decode_window() { return g_decode_window.load(std::memory_order_relaxed) != 0; }
+std::atomic<int> g_kmer_count_lds_max_k{7};  // largest k counted in the LDS table (kmer_count_kernels.hpp kKmerCountLdsMaxK, shipped); 0..7, for the A/B of the split
+inline int tune_kmer_count_lds_max_k() { return g_kmer_count_lds_max_k.load(std::memory_order_relaxed); }
 // log2 of the size (nt) beyond which decode plans for a packed stream that no longer fits the Infinity Cache: -1 = the device's
 // (chip_info().cache_nt, the shipped rule), 0..40 forced -- 0 lets a 2^20-nt call walk the past-the-cache plan (turn placement +
 // bits_to_n_window) at every packed phase with guard pages around it (its only coverage used to need 4 GiB of HBM)
@@ -133,6 +136,7 @@ constexpr int tune_round_trip_window_map() { return 0; }
 constexpr int tune_round_trip_plan() { return kRoundTripDefaultPlan; }
 constexpr int tune_decode_rot() { return -1; }
 constexpr bool tune_decode_window() { return true; }
+constexpr int tune_kmer_count_lds_max_k() { return 7; }  // kKmerCountLdsMaxK (kmer_count_kernels.hpp; asserted equal in kmer_count_abi.inc)
 inline uint64_t decode_cache_nt() { return chip_info().cache_nt; }
 #endif
 
@@ -692,6 +696,9 @@ int cnt_set_tuning(const char* key, int value) {
     } else if (!strcmp(key, "reduce_persistent")) {
         if (value < 0 || value > 1) return CNT_EINVAL;
         g_reduce_persistent.store(value);
+    } else if (!strcmp(key, "kmer_count_lds_max_k")) {
+        if (value < 0 || value > 7) return CNT_EINVAL;
+        g_kmer_count_lds_max_k.store(value);
     } else if (!strcmp(key, "hamming_order")) {
         if (value < 0 || value > 2) return CNT_EINVAL;
         g_hamming_order.store(value);
@@ -737,6 +744,7 @@ int cnt_get_tuning(const char* key, int* value) {
     else if (!strcmp(key, "decode_variants")) *value = kNumDecodeVariants;
     else if (!strcmp(key, "encode2_variants")) *value = kNumEncode2Variants;
     else if (!strcmp(key, "decode2_variants")) *value = kNumDecode2Variants;
+    else if (!strcmp(key, "kmer_count_lds_max_k")) *value = tune_kmer_count_lds_max_k();
 #ifdef CNT_LAB_VARIANTS
     else if (!strcmp(key, "launch_tiles")) *value = launch_tiles_override().load();
     else if (!strcmp(key, "decode_rot")) *value = g_decode_rot.load();
@@ -880,3 +888,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "packed_ops_abi.inc"
 #include "kmer_abi.inc"
 #include "minimizer_abi.inc"
+#include "kmer_count_abi.inc"

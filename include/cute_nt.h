@@ -137,8 +137,10 @@ int cnt_host_tier_info(int *device, int *numa_node, int *helper_cpus, int *stagi
  * signature (&[u8] -> Vec<u64>) allocates per call and cannot use this; the `_into` forms of the mirrors with buffers from
  * cnt_host_alloc can (rust/src/hip.rs PinnedBuf, cute_nucleotides.hpp PinnedBuffer, cute_nucleotides_amd.pinned_empty).
  * The packed-domain host entry points (cnt_hamming, cnt_complement, cnt_reverse_complement, cnt_validate, cnt_kmers,
- * cnt_minimizers) do the same: with ALL their slices pinned they run their kernels over the link instead of copying whole
- * buffers through device scratch (an in-place (reverse) complement, and cnt_minimizers with no room for a result, are staged).
+ * cnt_minimizers, cnt_kmer_counts) do the same: with ALL their slices pinned they run their kernels over the link instead of
+ * copying whole buffers through device scratch (an in-place (reverse) complement, and cnt_minimizers with no room for a result,
+ * are staged).  cnt_kmer_counts does it for its packed input only: its table is never used in place -- it is accumulated in
+ * device memory and copied back, pinned or not, because the kernel's atomic adds must not travel over the link.
  * CNT_HOST_PINNED=0: never look, always stage (A/B).
  *
  * cnt_host_alloc      *p = `bytes` of pinned, device-mapped host memory (the runtime places it on the current GPU's NUMA node);
@@ -379,6 +381,31 @@ int cnt_validate(const uint8_t *n, size_t n_len, unsigned flags, uint64_t *inval
 #define CNT_KMER_CANONICAL 0x10u
 int cnt_kmers_dev(const void *d_bits, size_t len, unsigned k, unsigned flags, void *d_out, size_t out_cap, void *stream);
 int cnt_kmers(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *out, size_t out_cap);
+
+/* k-mer counts, 1 <= k <= CNT_KMER_COUNTS_MAX_K = 12: the spectrum of the sequence as a dense table of 4^k u64 (k = 12: 128 MiB).
+ * With m = len-k+1 k-mers (len < k: none) and x_i = the value cnt_kmers writes for k-mer i with the same flags (0, or
+ * CNT_KMER_CANONICAL):
+ *   counts[v] = #{ i < m : x_i == v },  v in [0, 4^k)
+ * k = 1 is base composition (A, C, T, G in code order 0..3), k = 4 with CNT_KMER_CANONICAL the tetranucleotide vector.  With
+ * CNT_KMER_CANONICAL only canonical values receive counts: the bins of the other values stay as they were (device tier) or zero
+ * (host tier).  Input bits beyond len are ignored; counts[4^k .. counts_cap) is never written.
+ * Errors, before any device work: k == 0, k > 12, an unknown flag, a NULL or not 8-B aligned pointer when there is work, a table
+ * overlapping the input words: CNT_EINVAL; counts_cap < 4^k: CNT_ECAP.  len < k: CNT_OK -- the device tier touches nothing
+ * (whatever its pointers are), the host tier still writes its 4^k zeros (so its table is checked at every len).
+ * Device tier: ADDS to a table the caller zeroed, like the counters of cnt_hamming_dev / cnt_validate_dev -- one spectrum can be
+ *   accumulated over many sequences or chunks.  Enqueue-only, ONE launch: no allocation, no synchronisation, no scratch,
+ *   capturable in a graph; d_bits at any 8-B phase, len up to 2^36.  k <= 7 counts in a 64-KiB LDS table per workgroup (32-bit
+ *   counters, replicated for k <= 5, flushed with 64-bit atomics; the launcher bounds what a workgroup sees before its flush
+ *   below 2^32 k-mers), k >= 8 adds straight into the table with 64-bit global atomics.
+ *   Cost depends on the data: a lane folds equal consecutive k-mers into one add, so homopolymer runs are cheap, but short-period
+ *   repeats (ACAC..., ACGACG...) send every lane to the same few bins and their adds serialise.  Measured (DESIGN.md "k-mer
+ *   counts", profiles/kmer_counts_bench.jsonl): k <= 7 takes 0.20-0.42 ms for 2^30 nt on random and on all-A input alike
+ *   (all-A / random = 0.90-1.00); k >= 8 takes 45 ms on random input and, with every folded add on ONE word, 8.9 x the random
+ *   time on all-A input (25 ms against 2.8 ms at 2^26 nt, ~83 adds per microsecond): a cliff of this regime that remains.
+ * Host tier: SETS all 4^k entries, synchronous.  Pinned input is read in place; the table never is (see "pinned caller memory"). */
+#define CNT_KMER_COUNTS_MAX_K 12
+int cnt_kmer_counts_dev(const void *d_bits, size_t len, unsigned k, unsigned flags, void *d_counts, size_t counts_cap, void *stream);
+int cnt_kmer_counts(const uint64_t *bits, size_t len, unsigned k, unsigned flags, uint64_t *counts, size_t counts_cap);
 
 /* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
  *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m

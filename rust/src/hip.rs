@@ -66,6 +66,8 @@ extern "C" {
     fn cnt_validate(n: *const u8, n_len: usize, flags: c_uint, invalid: *mut u64) -> c_int;
     fn cnt_kmers_dev(d_bits: *const c_void, len: usize, k: c_uint, flags: c_uint, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
     fn cnt_kmers(bits: *const u64, len: usize, k: c_uint, flags: c_uint, out: *mut u64, out_cap: usize) -> c_int;
+    fn cnt_kmer_counts_dev(d_bits: *const c_void, len: usize, k: c_uint, flags: c_uint, d_counts: *mut c_void, counts_cap: usize, stream: *mut c_void) -> c_int;
+    fn cnt_kmer_counts(bits: *const u64, len: usize, k: c_uint, flags: c_uint, counts: *mut u64, counts_cap: usize) -> c_int;
     fn cnt_minimizers_work_bytes(len: usize, k: c_uint, w: c_uint, bytes: *mut usize) -> c_int;
     fn cnt_minimizers_dev(d_bits: *const c_void, len: usize, k: c_uint, w: c_uint, flags: c_uint, d_pos: *mut c_void, d_val: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_minimizers(bits: *const u64, len: usize, k: c_uint, w: c_uint, flags: c_uint, pos: *mut u64, val: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
@@ -449,6 +451,23 @@ pub fn kmers_hip(bits: &[u64], len: usize, k: u32, canonical: bool) -> Vec<u64> 
     res
 }
 
+/// The k-mer spectrum (`1 <= k <= 12`): `4^k` counts, entry `v` the number of k-mers whose `kmers_hip` value (same
+/// `canonical`) is `v`.  `k = 1` is base composition in code order A, C, T, G.
+pub fn kmer_counts_hip(bits: &[u64], len: usize, k: u32, canonical: bool) -> Vec<u64> {
+    need(bits, len);
+    if k == 0 || k > 12 {
+        panic!("k must be in 1..12");
+    }
+    let bins = 1usize << (2 * k);
+    let mut res: Vec<u64> = Vec::with_capacity(bins);
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    unsafe {
+        check(cnt_kmer_counts(bits.as_ptr(), len, k, flags, res.as_mut_ptr(), bins));
+        res.set_len(bins);
+    }
+    res
+}
+
 /// The (w,k)-minimizers (`1 <= k <= 32`, `1 <= w <= 256`): in each window of `w` consecutive k-mers the position with the
 /// smallest `(fmix64(k-mer), position)`, each distinct position once, ascending; returns the positions and their k-mers
 /// (forward, or canonical as in `kmers_hip`).  No window (`len < k + w - 1`): two empty vectors.
@@ -573,6 +592,16 @@ pub fn kmers_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, canonical: bool,
     }
     let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
     unsafe { check(cnt_kmers_dev(d_bits.ptr, len, k, flags, d_out.ptr, d_out.bytes / 8, std::ptr::null_mut())) };
+}
+
+/// Enqueue the k-mer spectrum of `len` device-resident nucleotides: ADDS to the `4^k` u64 counters in `d_counts` (>= that many
+/// words, zeroed by the caller before the first call); see `kmer_counts_hip`.
+pub fn kmer_counts_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, canonical: bool, d_counts: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    let flags = if canonical { CNT_KMER_CANONICAL } else { 0 };
+    unsafe { check(cnt_kmer_counts_dev(d_bits.ptr, len, k, flags, d_counts.ptr, d_counts.bytes / 8, std::ptr::null_mut())) };
 }
 
 /// Bytes of device scratch `minimizers_hip_dev` needs for this call (0 when there is no window).
