@@ -1,6 +1,8 @@
 """Operations on 2-bit packed nucleotides without decoding: Hamming distance,
 complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
-(w,k)-minimizers, approximate pattern search on one or both strands, and alphabet validation of ASCII buffers.  The reference does
+(w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
+windows of one length at the positions a search reported, forward or reverse-complemented), and alphabet validation of ASCII
+buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -9,7 +11,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, check, lib
+from ._lib import CNT_EXTRACT_REVCOMP, CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, check, lib
 from .n_to_bits import _counter, _dev_guard, _enqueue, _out_words, _p, _u8, _u64
 
 CNT_ALLOW_N = 0x2
@@ -183,6 +185,66 @@ def find_pattern_hip(bits, length, pattern, max_mismatches=0, both_strands=False
         return pos[: n.value], (inf[: n.value] if info else None)
 
 
+def _subseq_bounds(length, start, sub_len):
+    start, sub_len = int(start), int(sub_len)
+    if start < 0 or sub_len < 0 or start > length or sub_len > length - start:
+        raise ValueError("the subsequence [%d, %d + %d) does not lie inside the %d nucleotides" % (start, start, sub_len, length))
+    return start, sub_len
+
+
+def _region_len(region_len):
+    region_len = int(region_len)
+    if region_len < 0:
+        raise ValueError("region_len must not be negative")
+    return region_len
+
+
+def subseq_hip(bits, length, start, sub_len, revcomp=False):
+    """Nucleotides [start, start + sub_len) of the sequence as a packed sequence of their own (include/cute_nt.h "region
+    extraction"), np.uint64[words_for(sub_len)]; with revcomp=True their reverse complement.  `start` may be any nucleotide,
+    not only a multiple of 32.  Bounds outside the sequence raise ValueError."""
+    bits = _packed(bits, length)
+    start, sub_len = _subseq_bounds(length, start, sub_len)
+    out = np.empty(lib().cnt_words_for(sub_len), dtype=np.uint64)
+    check(lib().cnt_subseq(_p(bits), length, start, sub_len, CNT_EXTRACT_REVCOMP if revcomp else 0, _p(out), out.size))
+    return out
+
+
+def _regions(starts, info):
+    """the host tier's starts / info: contiguous uint64 arrays of one length"""
+    starts = np.asarray(starts)
+    if starts.dtype != np.uint64:
+        raise TypeError("starts must be a uint64 array")
+    starts = np.ascontiguousarray(starts).reshape(-1)
+    if info is not None:
+        info = np.asarray(info)
+        if info.dtype != np.uint64:
+            raise TypeError("info must be a uint64 array")
+        info = np.ascontiguousarray(info).reshape(-1)
+        if info.size != starts.size:
+            raise ValueError("info must have one entry per start")
+    return starts, info
+
+
+def extract_hip(bits, length, starts, region_len, info=None, revcomp=False):
+    """The n regions [starts[i], starts[i] + region_len) of the sequence (include/cute_nt.h "region extraction"): returns
+    (records, rejected), records np.uint64[n, R] with R = words_for(region_len), row i packed like a sequence of length
+    region_len.  Region i comes out reverse-complemented iff exactly one of `revcomp` and info[i] & CNT_FIND_REVERSE holds --
+    `info` may be the array find_pattern_hip returned, so that every hit reads as the pattern does.  A region that does not lie
+    inside the sequence is a row of zeros and is counted in `rejected`."""
+    bits = _packed(bits, length)
+    region_len = _region_len(region_len)
+    starts, info = _regions(starts, info)
+    n, R = starts.size, lib().cnt_words_for(region_len)
+    out = np.empty(n * R, dtype=np.uint64)
+    rejected = ctypes.c_uint64(0)
+    if bits.size == 0:
+        bits = np.zeros(1, dtype=np.uint64)  # no nucleotide: every region is rejected, but the library wants an address
+    check(lib().cnt_extract(_p(bits), length, _p(starts), _p(info) if info is not None else None, n, region_len,
+                            CNT_EXTRACT_REVCOMP if revcomp else 0, _p(out), out.size, ctypes.byref(rejected)))
+    return out.reshape(n, R), rejected.value
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -319,6 +381,51 @@ def find_pattern_dev(bits, length, pattern, max_mismatches=0, both_strands=False
              CNT_FIND_BOTH_STRANDS if both_strands else 0, ctypes.c_void_p(pos_p), ctypes.c_void_p(inf_p) if info else None, pos.numel(),
              ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
     return pos, (inf if info else None), count
+
+
+def subseq_dev(bits, length, start, sub_len, revcomp=False, out=None):
+    """Device tier of subseq_hip, enqueued on torch's current stream: `bits` an int64 CUDA tensor, the result the
+    [:words_for(sub_len)] view of an int64 tensor (`out` if given)."""
+    torch = _packed_dev(bits, length)
+    start, sub_len = _subseq_bounds(length, start, sub_len)
+    words = lib().cnt_words_for(sub_len)
+    out = _out_words(torch, out, words, bits)
+    if sub_len:
+        _enqueue(bits, lib().cnt_subseq_dev, ctypes.c_void_p(bits.data_ptr()), length, start, sub_len, CNT_EXTRACT_REVCOMP if revcomp else 0,
+                 ctypes.c_void_p(out.data_ptr()), out.numel())
+    return out[:words]
+
+
+def _regions_dev(torch, starts, info, like):
+    """the device tier's starts / info: contiguous int64 CUDA tensors of one length on the input's device"""
+    for name, t in (("starts", starts), ("info", info)):
+        if t is None:
+            continue
+        if not hasattr(t, "is_cuda") or t.dtype != torch.int64:
+            raise TypeError("%s must be an int64 tensor" % name)
+        if not t.is_cuda or not t.is_contiguous() or t.device != like.device or t.dim() != 1:
+            raise ValueError("%s must be a contiguous 1-d CUDA tensor on the input's device" % name)
+    if info is not None and info.numel() != starts.numel():
+        raise ValueError("info must have one entry per start")
+
+
+def extract_dev(bits, length, starts, region_len, info=None, revcomp=False, out=None, rejected=None):
+    """Device tier of extract_hip, enqueued on torch's current stream without a synchronisation: `starts` (and `info`, e.g. the
+    pos and info find_pattern_dev wrote) are int64 CUDA tensors holding the u64 values.  Returns (records, rejected): the
+    [n, R] view of an int64 tensor (`out` if given, >= n*R elements) and a 1-element int64 tensor the call ADDS the number of
+    rejected regions to (a fresh zeroed one unless the caller passes its own, which the caller zeroes)."""
+    torch = _packed_dev(bits, length)
+    region_len = _region_len(region_len)
+    _regions_dev(torch, starts, info, bits)
+    n, R = starts.numel(), lib().cnt_words_for(region_len)
+    out = _out_words(torch, out, n * R, bits)
+    rejected = _counter(torch, rejected, bits)
+    if n and region_len:
+        src = bits if bits.numel() else torch.zeros(1, dtype=torch.int64, device=bits.device)  # no nucleotide: every region is rejected
+        _enqueue(bits, lib().cnt_extract_dev, ctypes.c_void_p(src.data_ptr()), length, ctypes.c_void_p(starts.data_ptr()),
+                 ctypes.c_void_p(info.data_ptr()) if info is not None else None, n, region_len, CNT_EXTRACT_REVCOMP if revcomp else 0,
+                 ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(rejected.data_ptr()))
+    return out[: n * R].view(n, R), rejected
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -21,6 +21,7 @@
 //   minimizer_abi.inc   (w,k)-minimizers
 //   kmer_count_abi.inc  k-mer counts
 //   find_abi.inc        approximate pattern search
+//   extract_abi.inc     region extraction: subsequences and windows
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>
@@ -164,7 +165,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -891,3 +892,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "minimizer_abi.inc"
 #include "kmer_count_abi.inc"
 #include "find_abi.inc"
+#include "extract_abi.inc"

@@ -453,6 +453,50 @@ int cnt_find_pattern(const uint64_t *bits, size_t len, uint64_t pattern, unsigne
                      unsigned max_mismatches, unsigned flags, uint64_t *pos, uint64_t *info, size_t out_cap,
                      uint64_t *count);
 
+/* region extraction: n regions of one length out of a packed sequence, each written as a sequence of its own -- what samtools
+ * faidx / bedtools getfasta do for text, on the packed words and at any start (start % 32 != 0 included).  It acts on the
+ * positions cnt_minimizers and cnt_find_pattern report, and hands nucleotides [a, b) to every other call of this library.
+ *   R = cnt_words_for(region_len); record i occupies out[i*R .. (i+1)*R), packed exactly like a sequence of length region_len:
+ *       the bits of its last word at or above 2*(region_len % 32) are zero when region_len % 32 != 0
+ *   region i is REVERSED iff exactly one of these holds: flags has CNT_EXTRACT_REVCOMP; info != NULL and info[i] has
+ *       CNT_FIND_REVERSE.  All other bits of info[i] are ignored: the info array cnt_find_pattern wrote can be passed as it is,
+ *       and a reverse-strand hit then comes out as the sequence the pattern matched, read forward.
+ *   forward   code_out(i, j) = code(start[i] + j), j < region_len
+ *   reversed  code_out(i, j) = code(start[i] + region_len - 1 - j) ^ 2: the reverse complement of the forward record
+ *   cnt_subseq is the case n = 1, region_len = sub_len, with host-known bounds.
+ * Rejected regions (cnt_extract): region i is rejected when start[i] > len or region_len > len - start[i] -- a comparison that
+ *   never overflows, so start[i] = 2^64-1 is a rejected region and not a wrap-around.  Its record is written as R zero words and
+ *   it is counted once; the counter follows the reductions' convention, not the `count` of find and minimizers: *d_rejected is a
+ *   device u64 that the caller zeroed and the call ADDS to, *rejected (host tier) is SET; either may be NULL.  Whatever start
+ *   holds, no kernel reads outside the cnt_words_for(len) input words or writes outside out[0 .. n*R).
+ *   cnt_subseq: start > len or sub_len > len - start is CNT_EINVAL before any device work.
+ * Input bits beyond len are ignored.  out[n*R .. out_words) is never written.
+ * Empty work: n == 0 or region_len == 0 (sub_len == 0): CNT_OK, nothing is read or written (the host tier still sets
+ *   *rejected = 0).
+ * Errors, before any device work: an unknown flag; a NULL or not 8-B aligned bits, start or out, an info or rejected not 8-B
+ *   aligned, out overlapping bits, start or info, a region of 2^45 nt or more: CNT_EINVAL; n * R overflowing size_t or
+ *   out_words < n*R: CNT_ECAP.
+ * Device tier: enqueue-only (no allocation, no synchronisation, no scratch, capturable in a graph), pointers at any 8-B phase, len
+ *   and start may exceed 2^32.  One thread per output word (a gather: two dependent loads per word) for records below 512 words;
+ *   records of 512 words or more go through tiles of 512 output words (16384 nt) of one record, one workgroup each, whose source
+ *   word and bit phase are wave-uniform -- a 1 : 1 stream at an arbitrary bit phase, the loads of cnt_reverse_complement_dev's
+ *   tiles -- and the word kernel takes each record's last R % 512 words (and, for cnt_subseq_dev, the words in front of the first
+ *   128-B line of d_out).  With info both tile kernels walk every tile and each takes the records of its own orientation.
+ *   Measured on one MI355X, 2026-10-17, product build (DESIGN.md 4 "region extraction", profiles/extract_bench.jsonl): a 2^30-nt
+ *   subsequence takes 0.092-0.095 ms at phase 0 and 0.098-0.100 ms at a non-zero phase, forward and reversed, beside
+ *   cnt_reverse_complement_dev at 0.0895 ms (0.0874-0.0926) in the same run: 3-5 % over it plus its spread at a non-zero phase;
+ *   2^20 random windows of 23 / 101 / 1000 nt take 0.044 / 0.045 / 0.196 ms (0.045 / 0.047 / 0.213 ms with info, half reversed),
+ *   12x / 18x / 27x faster than torch indexing + integer ops on the packed words; 2^16 windows or fewer take 0.021 ms.
+ * Host tier: synchronous; pinned bits, start, info and out are used in place, everything else is staged. */
+#define CNT_EXTRACT_REVCOMP 0x40u
+int cnt_subseq_dev(const void *d_bits, size_t len, size_t start, size_t sub_len, unsigned flags, void *d_out, size_t out_words,
+                   void *stream);
+int cnt_subseq(const uint64_t *bits, size_t len, size_t start, size_t sub_len, unsigned flags, uint64_t *out, size_t out_words);
+int cnt_extract_dev(const void *d_bits, size_t len, const void *d_start, const void *d_info, size_t n, size_t region_len,
+                    unsigned flags, void *d_out, size_t out_words, void *d_rejected, void *stream);
+int cnt_extract(const uint64_t *bits, size_t len, const uint64_t *start, const uint64_t *info, size_t n, size_t region_len,
+                unsigned flags, uint64_t *out, size_t out_words, uint64_t *rejected);
+
 /* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
  *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m
  *   h_i   = fmix64(x_i), the splitmix64 finaliser mod 2^64: z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9,

@@ -74,6 +74,10 @@ extern "C" {
     fn cnt_find_pattern_work_bytes(len: usize, k: c_uint, bytes: *mut usize) -> c_int;
     fn cnt_find_pattern_dev(d_bits: *const c_void, len: usize, pattern: u64, k: c_uint, wildcards: u32, max_mismatches: c_uint, flags: c_uint, d_pos: *mut c_void, d_info: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_find_pattern(bits: *const u64, len: usize, pattern: u64, k: c_uint, wildcards: u32, max_mismatches: c_uint, flags: c_uint, pos: *mut u64, info: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
+    fn cnt_subseq_dev(d_bits: *const c_void, len: usize, start: usize, sub_len: usize, flags: c_uint, d_out: *mut c_void, out_words: usize, stream: *mut c_void) -> c_int;
+    fn cnt_subseq(bits: *const u64, len: usize, start: usize, sub_len: usize, flags: c_uint, out: *mut u64, out_words: usize) -> c_int;
+    fn cnt_extract_dev(d_bits: *const c_void, len: usize, d_start: *const c_void, d_info: *const c_void, n: usize, region_len: usize, flags: c_uint, d_out: *mut c_void, out_words: usize, d_rejected: *mut c_void, stream: *mut c_void) -> c_int;
+    fn cnt_extract(bits: *const u64, len: usize, start: *const u64, info: *const u64, n: usize, region_len: usize, flags: c_uint, out: *mut u64, out_words: usize, rejected: *mut u64) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -581,6 +585,56 @@ pub fn find_pattern_hip(bits: &[u64], len: usize, p: &Pattern, max_mismatches: u
     (pos, info)
 }
 
+const CNT_EXTRACT_REVCOMP: c_uint = 0x40;
+
+fn words_of(len: usize) -> usize {
+    (len >> 5) + if len & 31 != 0 { 1 } else { 0 }
+}
+
+/// Nucleotides `[start, start + sub_len)` of the sequence as a packed sequence of their own (`start` may be any nucleotide), or
+/// with `revcomp` their reverse complement.  Panics when the range does not lie inside the sequence.
+pub fn subseq_hip(bits: &[u64], len: usize, start: usize, sub_len: usize, revcomp: bool) -> Vec<u64> {
+    need(bits, len);
+    if start > len || sub_len > len - start {
+        panic!("the subsequence does not lie inside the sequence");
+    }
+    let words = words_of(sub_len);
+    let mut out: Vec<u64> = Vec::with_capacity(words);
+    let flags = if revcomp { CNT_EXTRACT_REVCOMP } else { 0 };
+    unsafe {
+        check(cnt_subseq(bits.as_ptr(), len, start, sub_len, flags, out.as_mut_ptr(), words));
+        out.set_len(words);
+    }
+    out
+}
+
+/// The regions `[start[i], start[i] + region_len)` of the sequence, record `i` in words `[i * R, (i + 1) * R)` of the result
+/// with `R = ceil(region_len / 32)`, packed like a sequence of length `region_len`; and the number of rejected regions (those
+/// that do not lie inside the sequence: their records are zero).  Region `i` is reverse-complemented iff exactly one of
+/// `revcomp` and `info[i] & FIND_REVERSE` holds: `info` may be what `find_pattern_hip` returned.
+pub fn extract_hip(bits: &[u64], len: usize, start: &[u64], info: Option<&[u64]>, region_len: usize, revcomp: bool) -> (Vec<u64>, u64) {
+    need(bits, len);
+    let n = start.len();
+    let info_ptr = match info {
+        Some(v) => {
+            if v.len() != n {
+                panic!("info must have one entry per start");
+            }
+            v.as_ptr()
+        }
+        None => std::ptr::null(),
+    };
+    let words = n.checked_mul(words_of(region_len)).expect("n * R overflows");
+    let mut out: Vec<u64> = Vec::with_capacity(words);
+    let flags = if revcomp { CNT_EXTRACT_REVCOMP } else { 0 };
+    let mut rejected: u64 = 0;
+    unsafe {
+        check(cnt_extract(bits.as_ptr(), len, start.as_ptr(), info_ptr, n, region_len, flags, out.as_mut_ptr(), words, &mut rejected));
+        out.set_len(words);
+    }
+    (out, rejected)
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -734,6 +788,46 @@ pub fn find_pattern_hip_dev(d_bits: &DeviceBuffer, len: usize, p: &Pattern, max_
         None => std::ptr::null_mut(),
     };
     unsafe { check(cnt_find_pattern_dev(d_bits.ptr, len, p.pattern, p.k, p.wildcards, max_mismatches, flags, d_pos.ptr, info_ptr, cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Enqueue the extraction of nucleotides `[start, start + sub_len)` of `len` device-resident ones into `d_out` (see
+/// `subseq_hip`).
+pub fn subseq_hip_dev(d_bits: &DeviceBuffer, len: usize, start: usize, sub_len: usize, revcomp: bool, d_out: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    if start > len || sub_len > len - start {
+        panic!("the subsequence does not lie inside the sequence");
+    }
+    let flags = if revcomp { CNT_EXTRACT_REVCOMP } else { 0 };
+    unsafe { check(cnt_subseq_dev(d_bits.ptr, len, start, sub_len, flags, d_out.ptr, d_out.bytes / 8, std::ptr::null_mut())) };
+}
+
+/// Enqueue the extraction of the `n` regions whose starts (u64) are in `d_start` (see `extract_hip`); `d_info`, when given, holds
+/// one u64 per region (what `find_pattern_hip_dev` wrote), and `d_rejected` (one u64 that the caller zeroed) has the number of
+/// rejected regions ADDED to it.
+pub fn extract_hip_dev(d_bits: &DeviceBuffer, len: usize, d_start: &DeviceBuffer, d_info: Option<&DeviceBuffer>, n: usize, region_len: usize, revcomp: bool, d_out: &DeviceBuffer, d_rejected: Option<&DeviceBuffer>) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    if n > d_start.bytes / 8 {
+        panic!("fewer starts than regions");
+    }
+    let info_ptr: *const c_void = match d_info {
+        Some(v) => {
+            if n > v.bytes / 8 {
+                panic!("info must have one entry per start");
+            }
+            v.ptr as *const c_void
+        }
+        None => std::ptr::null(),
+    };
+    let rejected_ptr = match d_rejected {
+        Some(v) => v.ptr,
+        None => std::ptr::null_mut(),
+    };
+    let flags = if revcomp { CNT_EXTRACT_REVCOMP } else { 0 };
+    unsafe { check(cnt_extract_dev(d_bits.ptr, len, d_start.ptr, info_ptr, n, region_len, flags, d_out.ptr, d_out.bytes / 8, rejected_ptr, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
