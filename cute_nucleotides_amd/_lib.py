@@ -26,6 +26,7 @@ CNT_KMER_CANONICAL = 0x10
 CNT_FIND_BOTH_STRANDS = 0x20
 CNT_FIND_REVERSE = 0x100  # in info[j] of cnt_find_pattern: the hit is on the reverse strand
 CNT_EXTRACT_REVCOMP = 0x40  # cnt_subseq / cnt_extract: every region comes out as its reverse complement
+CNT_TRANSLATE_REVCOMP = 0x80  # cnt_translate: the region is read as its reverse complement
 
 _vp, _sz, _u64, _int, _uint = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint
 
@@ -124,6 +125,8 @@ SIGNATURES = {
     "cnt_subseq": (_int, [_vp, _sz, _sz, _sz, _uint, _vp, _sz]),
     "cnt_extract_dev": (_int, [_vp, _sz, _vp, _vp, _sz, _sz, _uint, _vp, _sz, _vp, _vp]),
     "cnt_extract": (_int, [_vp, _sz, _vp, _vp, _sz, _sz, _uint, _vp, _sz, ctypes.POINTER(_u64)]),
+    "cnt_translate_dev": (_int, [_vp, _sz, _sz, _sz, _uint, _vp, _vp, _sz, _vp]),
+    "cnt_translate": (_int, [_vp, _sz, _sz, _sz, _uint, _vp, _vp, _sz]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

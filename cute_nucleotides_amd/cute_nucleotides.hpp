@@ -249,6 +249,24 @@ inline Vec<uint8_t> bits_to_n2_hip_sharded(const uint64_t* bits, size_t words, s
 
 }  // namespace n_to_bits2
 
+/// Operations on the packed words themselves (include/cute_nt.h): what needs no decode to ASCII.
+namespace packed {
+
+/// Nucleotides [start, start + sub_len) of the `len` packed in `bits` translated codon by codon (include/cute_nt.h "translation"):
+/// sub_len / 3 bytes, one entry of the 64-byte `table` per codon (nullptr: the standard genetic code, stops as '*'); with `revcomp`
+/// the translation of the region's reverse complement.  Forward frame f of a whole sequence is (f, len - f), reverse frame f is
+/// (0, len - f, true).
+inline Vec<uint8_t> translate_hip(const uint64_t* bits, size_t words, size_t len, size_t start, size_t sub_len, bool revcomp = false,
+                                  const uint8_t* table = nullptr) {
+    if (len > (words << 5)) detail::check(CNT_ELEN);
+    if (start > len || sub_len > len - start) throw std::out_of_range("translate_hip: the region does not lie inside the sequence");
+    Vec<uint8_t> out(sub_len / 3);
+    detail::check(cnt_translate(bits, len, start, sub_len, revcomp ? CNT_TRANSLATE_REVCOMP : 0u, table, out.data(), out.size()));
+    return out;
+}
+
+}  // namespace packed
+
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
 /// `DeviceBuffer` / `n_to_bits_hip_dev`, rust/src/hip.rs): data already in HBM, enqueue on the default stream,
 /// `sync()` waits.  This is the tier the roofline numbers measure.
@@ -294,6 +312,14 @@ inline void bits_to_n_hip_dev(const DeviceBuffer& bits, size_t words, size_t len
     if (len > (words << 5)) detail::check(CNT_ELEN);
     if (words * 8 > bits.size_bytes() || len > out.size_bytes()) throw std::out_of_range("bits_to_n_hip_dev: sizes");
     detail::check(cnt_bits_to_n_dev(bits.data(), words, len, out.data(), 0u, nullptr));
+}
+/// Enqueue the translation of nucleotides [start, start + sub_len) of `len` resident ones into `out` (>= sub_len / 3 bytes); see
+/// packed::translate_hip.  `table` is HOST memory, read before the call returns.
+inline void translate_hip_dev(const DeviceBuffer& bits, size_t len, size_t start, size_t sub_len, DeviceBuffer& out, bool revcomp = false,
+                              const uint8_t* table = nullptr) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    if (start > len || sub_len > len - start) throw std::out_of_range("translate_hip_dev: the region does not lie inside the sequence");
+    detail::check(cnt_translate_dev(bits.data(), len, start, sub_len, revcomp ? CNT_TRANSLATE_REVCOMP : 0u, table, out.data(), out.size_bytes(), nullptr));
 }
 inline void sync() { detail::check(cnt_dev_sync(nullptr)); }
 inline void set_device(int device) { detail::check(cnt_set_device(device)); }  // what DeviceBuffer allocates on

@@ -1,8 +1,8 @@
 """Operations on 2-bit packed nucleotides without decoding: Hamming distance,
 complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
 (w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
-windows of one length at the positions a search reported, forward or reverse-complemented), and alphabet validation of ASCII
-buffers.  The reference does
+windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
+frames, and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -11,8 +11,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import CNT_EXTRACT_REVCOMP, CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, check, lib
-from .n_to_bits import _counter, _dev_guard, _enqueue, _out_words, _p, _u8, _u64
+from ._lib import CNT_EXTRACT_REVCOMP, CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, CNT_TRANSLATE_REVCOMP, check, lib
+from .n_to_bits import _counter, _dev_guard, _enqueue, _out_bytes, _out_words, _p, _u8, _u64
 
 CNT_ALLOW_N = 0x2
 
@@ -245,6 +245,77 @@ def extract_hip(bits, length, starts, region_len, info=None, revcomp=False):
     return out.reshape(n, R), rejected.value
 
 
+# NCBI genetic codes as the NCBI prints them: one amino acid per codon in TCAG order, base 1 slowest
+_NCBI_CODES = {
+    1: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    2: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIMMTTTTNNKKSS**VVVVAAAADDEEGGGG",
+    4: "FFLLSSSSYY**CCWWLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+    11: "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG",
+}
+_TCAG_CODES = (2, 1, 0, 3)  # the codes (A0 C1 T2 G3) of T, C, A, G
+
+
+def codon_table(ncbi_id=1):
+    """The 64-byte translation table of an NCBI genetic code (1 standard, 2 vertebrate mitochondrial, 4 mold / protozoan
+    mitochondrial and mycoplasma, 11 bacterial; stops as `*`) in the library's index order: entry c = x0 | x1 << 2 | x2 << 4 is
+    the amino acid of the codon whose bases have the codes x0, x1, x2 (include/cute_nt.h "translation")."""
+    if ncbi_id not in _NCBI_CODES:
+        raise ValueError("genetic code %r is not one of %s" % (ncbi_id, sorted(_NCBI_CODES)))
+    aas = _NCBI_CODES[ncbi_id]
+    table = bytearray(64)
+    for i, x0 in enumerate(_TCAG_CODES):
+        for j, x1 in enumerate(_TCAG_CODES):
+            for k, x2 in enumerate(_TCAG_CODES):
+                table[x0 | x1 << 2 | x2 << 4] = ord(aas[16 * i + 4 * j + k])
+    return bytes(table)
+
+
+def _codon_table(table):
+    """a table argument as the 64 bytes the library reads (None: its built-in standard code)"""
+    if table is None:
+        return None
+    if isinstance(table, (bytes, bytearray)):
+        table = bytes(table)
+    elif isinstance(table, np.ndarray):
+        if table.dtype != np.uint8:
+            raise TypeError("a translation table is 64 bytes: bytes or a uint8 array")
+        table = np.ascontiguousarray(table).tobytes()
+    else:
+        raise TypeError("a translation table is 64 bytes: bytes or a uint8 array")
+    if len(table) != 64:
+        raise ValueError("a translation table has 64 entries, not %d" % len(table))
+    return table
+
+
+def _translate_region(length, start, sub_len):
+    return _subseq_bounds(length, start, length - int(start) if sub_len is None else sub_len)
+
+
+def _six_frames(length):
+    """(start, sub_len, revcomp) of the frames +0, +1, +2, -0, -1, -2 of a whole sequence (a frame past its end is empty)"""
+    skip = [min(f, length) for f in range(3)]
+    return [(f, length - f, False) for f in skip] + [(0, length - f, True) for f in skip]
+
+
+def translate_hip(bits, length, start=0, sub_len=None, revcomp=False, table=None):
+    """Nucleotides [start, start + sub_len) of the sequence (sub_len=None: to its end) translated codon by codon (include/cute_nt.h
+    "translation"): np.uint8[sub_len // 3], one byte of `table` per codon; with revcomp=True the region is read as its reverse
+    complement.  `table` is 64 bytes (bytes or a uint8 array, e.g. codon_table(11)); None is the standard genetic code with stops
+    as `*`.  Forward frame f of a whole sequence is start=f; reverse frame f is sub_len=length - f with revcomp=True."""
+    bits = _packed(bits, length)
+    start, sub_len = _translate_region(length, start, sub_len)
+    table = _codon_table(table)
+    out = np.empty(sub_len // 3, dtype=np.uint8)
+    if sub_len >= 3:
+        check(lib().cnt_translate(_p(bits), length, start, sub_len, CNT_TRANSLATE_REVCOMP if revcomp else 0, table, _p(out), out.size))
+    return out
+
+
+def six_frames_hip(bits, length, table=None):
+    """The six translations of the whole sequence, in the order +0, +1, +2, -0, -1, -2 (see translate_hip)."""
+    return [translate_hip(bits, length, start, sub_len, rev, table) for start, sub_len, rev in _six_frames(length)]
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -426,6 +497,26 @@ def extract_dev(bits, length, starts, region_len, info=None, revcomp=False, out=
                  ctypes.c_void_p(info.data_ptr()) if info is not None else None, n, region_len, CNT_EXTRACT_REVCOMP if revcomp else 0,
                  ctypes.c_void_p(out.data_ptr()), out.numel(), ctypes.c_void_p(rejected.data_ptr()))
     return out[: n * R].view(n, R), rejected
+
+
+def translate_dev(bits, length, start=0, sub_len=None, revcomp=False, table=None, out=None):
+    """Device tier of translate_hip, enqueued on torch's current stream: `bits` an int64 CUDA tensor, the result the
+    [:sub_len // 3] view of a uint8 tensor (`out` if given, at any byte address).  `table` is HOST memory (bytes or a uint8 numpy
+    array): the library reads it before this call returns."""
+    torch = _packed_dev(bits, length)
+    start, sub_len = _translate_region(length, start, sub_len)
+    table = _codon_table(table)
+    m = sub_len // 3
+    out = _out_bytes(torch, out, m, bits)
+    if sub_len >= 3:
+        _enqueue(bits, lib().cnt_translate_dev, ctypes.c_void_p(bits.data_ptr()), length, start, sub_len, CNT_TRANSLATE_REVCOMP if revcomp else 0,
+                 table, ctypes.c_void_p(out.data_ptr()), out.numel())
+    return out[:m]
+
+
+def six_frames_dev(bits, length, table=None):
+    """Device tier of six_frames_hip: six uint8 CUDA tensors in the order +0, +1, +2, -0, -1, -2."""
+    return [translate_dev(bits, length, start, sub_len, rev, table) for start, sub_len, rev in _six_frames(length)]
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -22,6 +22,7 @@
 //   kmer_count_abi.inc  k-mer counts
 //   find_abi.inc        approximate pattern search
 //   extract_abi.inc     region extraction: subsequences and windows
+//   translate_abi.inc   codon translation, any frame, either strand
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>
@@ -165,7 +166,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -893,3 +894,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "kmer_count_abi.inc"
 #include "find_abi.inc"
 #include "extract_abi.inc"
+#include "translate_abi.inc"

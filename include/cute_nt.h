@@ -497,6 +497,47 @@ int cnt_extract_dev(const void *d_bits, size_t len, const void *d_start, const v
 int cnt_extract(const uint64_t *bits, size_t len, const uint64_t *start, const uint64_t *info, size_t n, size_t region_len,
                 unsigned flags, uint64_t *out, size_t out_words, uint64_t *rejected);
 
+/* translation: nucleotides [start, start + sub_len) of a packed sequence read as codons, one output byte per codon, in any of
+ * the six frames -- the first step of an ORF scan or a protein search, without a decode to ASCII.
+ *   codon value of three consecutive codes (A=0 C=1 T=2 G=3): c = x0 | x1 << 2 | x2 << 4, the value cnt_kmers writes for k = 3
+ *   table      64 bytes, table[c] the output byte for codon c; NULL: the standard genetic code (NCBI table 1, stops as '*'),
+ *              in this index order
+ *                  KQ*ETPSAILLVRR*GNHYDTPSAILFVSRCGNHYDTPSAILFVSRCGKQ*ETPSAMLLVRRWG
+ *              A HOST pointer in both tiers: its 64 bytes are read before the call returns and travel as kernel arguments, so the
+ *              device call stays enqueue-only and the caller may free or change the table right after it.  Any 64 bytes are
+ *              legal; they are not validated.
+ *   M = sub_len / 3 output bytes; the last sub_len % 3 nucleotides of the region, as read, are ignored
+ *   forward    out[j] = table[codon(start + 3j)], codon(p) = code(p) | code(p+1) << 2 | code(p+2) << 4
+ *   CNT_TRANSLATE_REVCOMP   the region is read as its reverse complement, as cnt_subseq with CNT_EXTRACT_REVCOMP does:
+ *              r(i) = code(start + sub_len - 1 - i) ^ 2,  out[j] = table[r(3j) | r(3j+1) << 2 | r(3j+2) << 4]
+ *   the six frames of a whole sequence: forward frame f is (start = f, sub_len = len - f), reverse frame f is
+ *              (start = 0, sub_len = len - f, CNT_TRANSLATE_REVCOMP)
+ * out_cap is in bytes; out[M .. out_cap) is never written.  Input bits beyond len are ignored.
+ * The checks, in this order and all before any device work:
+ *   1. an unknown flag: CNT_EINVAL, even without work
+ *   2. sub_len < 3: CNT_OK, nothing is read or written, whatever the pointers and start are
+ *   3. start > len or sub_len > len - start: CNT_EINVAL
+ *   4. a NULL bits or out, bits not 8-B aligned, out[0 .. M) overlapping the cnt_words_for(len) input words: CNT_EINVAL
+ *   5. out_cap < M: CNT_ECAP
+ * Device tier: enqueue-only (no allocation, no synchronisation, no scratch, capturable in a graph), d_bits at any 8-B phase,
+ *   d_out at any byte address, len and start may exceed 2^32.  Tiles of 4096 output bytes (12288 nt), one workgroup each, start
+ *   at the first 16-B boundary of d_out: the source dword and bit phase are wave-uniform, a lane reads 96 bits (three dwords, and
+ *   a fourth for the phase), looks its 16 codons up in the table staged in 64 B of LDS and issues one 16-B store.  The reverse
+ *   strand is the same stream walked downward with the table composed with the codon's reverse complement.  One thread per byte
+ *   takes what lies in front of the boundary and behind the last whole tile, and all of a call with no whole tile behind the
+ *   boundary (M < head + 4096, head the bytes in front of it): no tile starts off a 16-B boundary.
+ *   Measured on one MI355X, 2026-10-18, product build (DESIGN.md 4 "translation", profiles/translate_bench.jsonl): 2^30 nt take
+ *   0.106-0.107 ms at start 0, forward and reversed, and 0.116-0.120 ms at start 1 / 2 / 17 (5.8-5.9 and 5.2-5.4 TB/s of
+ *   0.25 + 1/3 B per nt), beside cnt_bits_to_n_dev on 2^30 nt at 0.1884 ms (0.1858-0.2064; 7.12 TB/s of 1.25 B per nt) in the
+ *   same run: 0.82-0.83 of decode's achieved bandwidth at bit phase 0, 0.74-0.76 at a non-zero phase; a custom table costs what
+ *   the standard one does.
+ * Host tier: synchronous; pinned bits and out are used in place, everything else is staged. */
+#define CNT_TRANSLATE_REVCOMP 0x80u
+int cnt_translate_dev(const void *d_bits, size_t len, size_t start, size_t sub_len, unsigned flags, const uint8_t *table,
+                      void *d_out, size_t out_cap, void *stream);
+int cnt_translate(const uint64_t *bits, size_t len, size_t start, size_t sub_len, unsigned flags, const uint8_t *table,
+                  uint8_t *out, size_t out_cap);
+
 /* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
  *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m
  *   h_i   = fmix64(x_i), the splitmix64 finaliser mod 2^64: z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9,

@@ -78,6 +78,8 @@ extern "C" {
     fn cnt_subseq(bits: *const u64, len: usize, start: usize, sub_len: usize, flags: c_uint, out: *mut u64, out_words: usize) -> c_int;
     fn cnt_extract_dev(d_bits: *const c_void, len: usize, d_start: *const c_void, d_info: *const c_void, n: usize, region_len: usize, flags: c_uint, d_out: *mut c_void, out_words: usize, d_rejected: *mut c_void, stream: *mut c_void) -> c_int;
     fn cnt_extract(bits: *const u64, len: usize, start: *const u64, info: *const u64, n: usize, region_len: usize, flags: c_uint, out: *mut u64, out_words: usize, rejected: *mut u64) -> c_int;
+    fn cnt_translate_dev(d_bits: *const c_void, len: usize, start: usize, sub_len: usize, flags: c_uint, table: *const u8, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
+    fn cnt_translate(bits: *const u64, len: usize, start: usize, sub_len: usize, flags: c_uint, table: *const u8, out: *mut u8, out_cap: usize) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -635,6 +637,34 @@ pub fn extract_hip(bits: &[u64], len: usize, start: &[u64], info: Option<&[u64]>
     (out, rejected)
 }
 
+const CNT_TRANSLATE_REVCOMP: c_uint = 0x80;
+
+fn table_ptr(table: Option<&[u8; 64]>) -> *const u8 {
+    match table {
+        Some(t) => t.as_ptr(),
+        None => std::ptr::null(),
+    }
+}
+
+/// Nucleotides `[start, start + sub_len)` of the sequence translated codon by codon: `sub_len / 3` bytes, one entry of `table`
+/// per codon (index `x0 | x1 << 2 | x2 << 4` of the codes A0 C1 T2 G3; `None` is the standard genetic code with stops as `*`),
+/// or with `revcomp` the translation of the region's reverse complement.  Forward frame `f` of a whole sequence is
+/// `(f, len - f, false)`, reverse frame `f` is `(0, len - f, true)`.  Panics when the range does not lie inside the sequence.
+pub fn translate_hip(bits: &[u64], len: usize, start: usize, sub_len: usize, revcomp: bool, table: Option<&[u8; 64]>) -> Vec<u8> {
+    need(bits, len);
+    if start > len || sub_len > len - start {
+        panic!("the region does not lie inside the sequence");
+    }
+    let m = sub_len / 3;
+    let mut out: Vec<u8> = Vec::with_capacity(m);
+    let flags = if revcomp { CNT_TRANSLATE_REVCOMP } else { 0 };
+    unsafe {
+        check(cnt_translate(bits.as_ptr(), len, start, sub_len, flags, table_ptr(table), out.as_mut_ptr(), m));
+        out.set_len(m);
+    }
+    out
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -828,6 +858,19 @@ pub fn extract_hip_dev(d_bits: &DeviceBuffer, len: usize, d_start: &DeviceBuffer
     };
     let flags = if revcomp { CNT_EXTRACT_REVCOMP } else { 0 };
     unsafe { check(cnt_extract_dev(d_bits.ptr, len, d_start.ptr, info_ptr, n, region_len, flags, d_out.ptr, d_out.bytes / 8, rejected_ptr, std::ptr::null_mut())) };
+}
+
+/// Enqueue the translation of nucleotides `[start, start + sub_len)` of `len` device-resident ones into the `sub_len / 3` bytes of
+/// `d_out` (see `translate_hip`).  `table` is host memory, read before the call returns.
+pub fn translate_hip_dev(d_bits: &DeviceBuffer, len: usize, start: usize, sub_len: usize, revcomp: bool, table: Option<&[u8; 64]>, d_out: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    if start > len || sub_len > len - start {
+        panic!("the region does not lie inside the sequence");
+    }
+    let flags = if revcomp { CNT_TRANSLATE_REVCOMP } else { 0 };
+    unsafe { check(cnt_translate_dev(d_bits.ptr, len, start, sub_len, flags, table_ptr(table), d_out.ptr, d_out.bytes, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
