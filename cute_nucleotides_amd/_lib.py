@@ -27,6 +27,11 @@ CNT_FIND_BOTH_STRANDS = 0x20
 CNT_FIND_REVERSE = 0x100  # in info[j] of cnt_find_pattern: the hit is on the reverse strand
 CNT_EXTRACT_REVCOMP = 0x40  # cnt_subseq / cnt_extract: every region comes out as its reverse complement
 CNT_TRANSLATE_REVCOMP = 0x80  # cnt_translate: the region is read as its reverse complement
+CNT_ORF_BOTH_STRANDS = 0x200
+CNT_ORF_OPEN_END = 0x400  # in info[j] of cnt_orfs: the ORF's opening bound is the end of the sequence, not a stop codon
+CNT_ORF_NO_STOP = 0x800  # in info[j] of cnt_orfs: the ORF's closing bound is the end of the sequence, not a stop codon
+CNT_ORF_STOPS_STANDARD = (1 << 2) | (1 << 14) | (1 << 50)  # TAA TGA TAG
+CNT_ORF_STARTS_ATG = 1 << 56
 
 _vp, _sz, _u64, _int, _uint = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint
 
@@ -127,6 +132,9 @@ SIGNATURES = {
     "cnt_extract": (_int, [_vp, _sz, _vp, _vp, _sz, _sz, _uint, _vp, _sz, ctypes.POINTER(_u64)]),
     "cnt_translate_dev": (_int, [_vp, _sz, _sz, _sz, _uint, _vp, _vp, _sz, _vp]),
     "cnt_translate": (_int, [_vp, _sz, _sz, _sz, _uint, _vp, _vp, _sz]),
+    "cnt_orfs_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
+    "cnt_orfs_dev": (_int, [_vp, _sz, _u64, _u64, _sz, _uint, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_orfs": (_int, [_vp, _sz, _u64, _u64, _sz, _uint, _vp, _vp, _vp, _sz, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

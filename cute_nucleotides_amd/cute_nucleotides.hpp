@@ -265,6 +265,44 @@ inline Vec<uint8_t> translate_hip(const uint64_t* bits, size_t words, size_t len
     return out;
 }
 
+/// What packed::orfs_hip returns: entry j is the ORF [pos[j], pos[j] + length[j]) with info[j] = its frame plus CNT_FIND_REVERSE,
+/// CNT_ORF_OPEN_END and CNT_ORF_NO_STOP.
+struct Orfs {
+    Vec<uint64_t> pos, length, info;
+};
+
+/// The open reading frames of the `len` nucleotides packed in `bits` (include/cute_nt.h "ORF scan"): the stop-free runs of each
+/// frame lane, on the forward strand or with `both_strands` on both, trimmed to their first start codon (starts == 0: reported
+/// whole), at least `min_len` nucleotides long, ordered by the upper end of the run, forward before reverse.  `stops` and `starts`
+/// are 64-bit sets of codon values.  translate_hip(bits, words, len, pos[j], length[j], reverse) is the protein of entry j.
+inline Orfs orfs_hip(const uint64_t* bits, size_t words, size_t len, uint64_t stops = CNT_ORF_STOPS_STANDARD, uint64_t starts = CNT_ORF_STARTS_ATG,
+                     size_t min_len = 0, bool both_strands = false) {
+    if (len > (words << 5)) detail::check(CNT_ELEN);
+    if (stops == 0) throw std::invalid_argument("orfs_hip: stops must hold at least one codon");
+    const size_t most = len < 3 ? 0 : (both_strands ? 2 * len : len);
+    // random sequence: a stop every ~21 codons of a lane; a longer result is fetched again at its reported size
+    size_t cap = most < most / 16 + 1024 ? most : most / 16 + 1024;
+    const unsigned flags = both_strands ? CNT_ORF_BOTH_STRANDS : 0u;
+    Orfs r;
+    uint64_t n = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        r.pos.resize(cap);
+        r.length.resize(cap);
+        r.info.resize(cap);
+        const int rc = cnt_orfs(bits, len, stops, starts, min_len, flags, r.pos.data(), r.length.data(), r.info.data(), cap, &n);
+        if (rc == CNT_ECAP && attempt == 0) {
+            cap = n;
+            continue;
+        }
+        detail::check(rc);
+        break;
+    }
+    r.pos.resize(n);
+    r.length.resize(n);
+    r.info.resize(n);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -320,6 +358,23 @@ inline void translate_hip_dev(const DeviceBuffer& bits, size_t len, size_t start
     if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
     if (start > len || sub_len > len - start) throw std::out_of_range("translate_hip_dev: the region does not lie inside the sequence");
     detail::check(cnt_translate_dev(bits.data(), len, start, sub_len, revcomp ? CNT_TRANSLATE_REVCOMP : 0u, table, out.data(), out.size_bytes(), nullptr));
+}
+inline size_t orfs_work_bytes(size_t len) {
+    size_t bytes = 0;
+    detail::check(cnt_orfs_work_bytes(len, &bytes));
+    return bytes;
+}
+/// Enqueue the ORF scan of `len` resident nucleotides (see packed::orfs_hip): `count` (one u64) is SET to the number of entries n,
+/// the first min(n, capacity) go to `pos`, `length` and, when given, `info`; `work` holds >= orfs_work_bytes(len) bytes of any
+/// contents.
+inline void orfs_hip_dev(const DeviceBuffer& bits, size_t len, uint64_t stops, uint64_t starts, size_t min_len, bool both_strands, DeviceBuffer& pos,
+                         DeviceBuffer& length, DeviceBuffer* info, DeviceBuffer& count, DeviceBuffer& work) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    if (stops == 0) throw std::invalid_argument("orfs_hip_dev: stops must hold at least one codon");
+    size_t cap = (pos.size_bytes() < length.size_bytes() ? pos.size_bytes() : length.size_bytes()) / 8;
+    if (info && info->size_bytes() / 8 < cap) cap = info->size_bytes() / 8;
+    detail::check(cnt_orfs_dev(bits.data(), len, stops, starts, min_len, both_strands ? CNT_ORF_BOTH_STRANDS : 0u, pos.data(), length.data(),
+                               info ? info->data() : nullptr, cap, count.data(), work.data(), work.size_bytes(), nullptr));
 }
 inline void sync() { detail::check(cnt_dev_sync(nullptr)); }
 inline void set_device(int device) { detail::check(cnt_set_device(device)); }  // what DeviceBuffer allocates on

@@ -2,7 +2,7 @@
 complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
 (w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
-frames, and alphabet validation of ASCII buffers.  The reference does
+frames, the open-reading-frame scan on one or both strands, and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -11,7 +11,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import CNT_EXTRACT_REVCOMP, CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, CNT_TRANSLATE_REVCOMP, check, lib
+from ._lib import (CNT_EXTRACT_REVCOMP, CNT_FIND_BOTH_STRANDS, CNT_FIND_REVERSE, CNT_KMER_CANONICAL, CNT_ORF_BOTH_STRANDS, CNT_ORF_NO_STOP,
+                   CNT_ORF_OPEN_END, CNT_ORF_STARTS_ATG, CNT_ORF_STOPS_STANDARD, CNT_TRANSLATE_REVCOMP, check, lib)
 from .n_to_bits import _counter, _dev_guard, _enqueue, _out_bytes, _out_words, _p, _u8, _u64
 
 CNT_ALLOW_N = 0x2
@@ -316,6 +317,68 @@ def six_frames_hip(bits, length, table=None):
     return [translate_hip(bits, length, start, sub_len, rev, table) for start, sub_len, rev in _six_frames(length)]
 
 
+def codon_set(codons):
+    """The 64-bit set of codon values (include/cute_nt.h "ORF scan") of an iterable of three-letter codons spelled in ACGTU
+    (either case): bit x0 | x1 << 2 | x2 << 4 for the codes (A0 C1 T2 G3) of each.  Anything else raises ValueError."""
+    if isinstance(codons, (str, bytes, bytearray)):
+        raise ValueError("a codon set is a list of three-letter codons, not one string")
+    mask = 0
+    for codon in codons:
+        if isinstance(codon, (bytes, bytearray)):
+            codon = bytes(codon).decode("latin-1")
+        if not isinstance(codon, str) or len(codon) != 3 or any(ch not in _PATTERN_CODES for ch in codon.upper()):
+            raise ValueError("codon %r is not three letters of ACGTU" % (codon,))
+        x = [_PATTERN_CODES[ch] for ch in codon.upper()]
+        mask |= 1 << (x[0] | x[1] << 2 | x[2] << 4)
+    return mask
+
+
+def _orf_args(stops, starts, min_len):
+    """the stops / starts arguments -- masks or lists of codons -- and min_len, checked as the library would"""
+    masks = []
+    for name, v in (("stops", stops), ("starts", starts)):
+        if v is None:
+            v = 0
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool):
+            v = codon_set(v)
+        v = int(v)
+        if v < 0 or v >> 64:
+            raise ValueError("%s must be a 64-bit set of codon values" % name)
+        masks.append(v)
+    if masks[0] == 0:
+        raise ValueError("stops must hold at least one codon")
+    min_len = int(min_len)
+    if min_len < 0:
+        raise ValueError("min_len must not be negative")
+    return masks[0], masks[1], min_len
+
+
+def orfs_hip(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_ATG, min_len=0, both_strands=False, info=True):
+    """The open reading frames of the sequence (include/cute_nt.h "ORF scan"): the stop-free runs of each frame lane, on the
+    forward strand or with both_strands=True on both, trimmed to their first start codon (starts=0 or None: reported whole), at
+    least min_len nucleotides long.  `stops` / `starts` are 64-bit sets of codon values or lists of codons for codon_set.
+    Returns numpy uint64 (pos, length, info) of n entries ordered by the upper end of the run, forward before reverse: info =
+    the frame, plus CNT_FIND_REVERSE, CNT_ORF_OPEN_END, CNT_ORF_NO_STOP (None with info=False) -- translate_hip(bits, length,
+    pos[j], length[j], revcomp=reverse) is the protein, and extract_hip takes pos and info as they are.  The output buffers
+    start at a guess of n and are sized to the reported n once if the guess was short."""
+    stops, starts, min_len = _orf_args(stops, starts, min_len)
+    bits = _packed(bits, length)
+    most = (2 * length if both_strands else length) if length >= 3 else 0
+    cap = min(most, most // 16 + 1024)  # random sequence: a stop every ~21 codons of a lane
+    flags = CNT_ORF_BOTH_STRANDS if both_strands else 0
+    for attempt in range(2):
+        pos = np.empty(cap, dtype=np.uint64)
+        lens = np.empty(cap, dtype=np.uint64)
+        inf = np.empty(cap, dtype=np.uint64) if info else None
+        n = ctypes.c_uint64(0)
+        rc = lib().cnt_orfs(_p(bits), length, stops, starts, min_len, flags, _p(pos), _p(lens), _p(inf) if info else None, cap, ctypes.byref(n))
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            cap = n.value
+            continue
+        check(rc)
+        return pos[: n.value], lens[: n.value], (inf[: n.value] if info else None)
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -517,6 +580,48 @@ def translate_dev(bits, length, start=0, sub_len=None, revcomp=False, table=None
 def six_frames_dev(bits, length, table=None):
     """Device tier of six_frames_hip: six uint8 CUDA tensors in the order +0, +1, +2, -0, -1, -2."""
     return [translate_dev(bits, length, start, sub_len, rev, table) for start, sub_len, rev in _six_frames(length)]
+
+
+def orfs_work_bytes(length):
+    """bytes of device scratch cnt_orfs_dev needs for a sequence of this length (0 below 3 nucleotides)"""
+    out = ctypes.c_size_t(0)
+    check(lib().cnt_orfs_work_bytes(length, ctypes.byref(out)))
+    return out.value
+
+
+def orfs_dev(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_ATG, min_len=0, both_strands=False, info=True, pos=None, lens=None,
+             work=None, count=None):
+    """Device tier of orfs_hip, enqueued on torch's current stream without a synchronisation: returns (pos, length, info,
+    count), int64 CUDA tensors, count a 1-element tensor that the call SETS to n; the [:n] views are the result once the stream
+    has run.  `info` is True (a fresh tensor), False (none is written, None is returned) or the int64 tensor to write, at least
+    as long as `pos`; a given `lens` is at least as long as `pos` too.  Without `pos` the outputs hold the most n can be (one
+    entry per nucleotide and strand); a given one of any capacity receives the first min(n, capacity) entries.  `work` (>=
+    orfs_work_bytes bytes, any contents) and `count` may be reused across calls, e.g. in a captured graph."""
+    stops, starts, min_len = _orf_args(stops, starts, min_len)
+    torch = _packed_dev(bits, length)
+    most = (2 * length if both_strands else length) if length >= 3 else 0
+    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(most, 1), dtype=torch.int64, device=bits.device)
+    lens = _out_words(torch, lens, pos.numel(), bits) if lens is not None else torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
+    if info is True:
+        inf = torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
+    elif info is False or info is None:
+        info = False
+    else:
+        inf, info = _out_words(torch, info, pos.numel(), bits), True
+    count = _out_words(torch, count, 1, bits)
+    need = orfs_work_bytes(length)
+    if work is None:
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
+    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
+        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
+    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    pos_p = pos.data_ptr() or count.data_ptr()
+    len_p = lens.data_ptr() or count.data_ptr()
+    inf_p = (inf.data_ptr() or count.data_ptr()) if info else None
+    _enqueue(bits, lib().cnt_orfs_dev, ctypes.c_void_p(bits.data_ptr()), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0,
+             ctypes.c_void_p(pos_p), ctypes.c_void_p(len_p), ctypes.c_void_p(inf_p) if info else None, pos.numel(),
+             ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
+    return pos, lens, (inf if info else None), count
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -23,6 +23,7 @@
 //   find_abi.inc        approximate pattern search
 //   extract_abi.inc     region extraction: subsequences and windows
 //   translate_abi.inc   codon translation, any frame, either strand
+//   orf_abi.inc         open-reading-frame scan, one strand or both
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>
@@ -166,7 +167,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -895,3 +896,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "find_abi.inc"
 #include "extract_abi.inc"
 #include "translate_abi.inc"
+#include "orf_abi.inc"

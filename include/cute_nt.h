@@ -538,6 +538,68 @@ int cnt_translate_dev(const void *d_bits, size_t len, size_t start, size_t sub_l
 int cnt_translate(const uint64_t *bits, size_t len, size_t start, size_t sub_len, unsigned flags, const uint8_t *table,
                   uint8_t *out, size_t out_cap);
 
+/* ORF scan: the open reading frames of a packed sequence, on the forward strand or on both, as (pos, length, info) entries that
+ * cnt_translate and cnt_extract take as they are -- the pipeline stays in packed words from end to end.
+ *   codons     a codon position is p in [0, len-3]; its value is c(p) = code(p) | code(p+1) << 2 | code(p+2) << 4, the value
+ *              cnt_kmers writes for k = 3 and cnt_translate indexes its table with
+ *   stops, starts   64-bit sets of codon values: bit c set = codon c is in the set.  On the forward strand position p is tested
+ *              with c(p), on the reverse strand with rc3(c(p)), rc3(c) = ((c >> 4) | (c & 0xC) | ((c & 3) << 4)) ^ 0x2A (the
+ *              codon's reverse complement, the composition cnt_translate applies to its table).  CNT_ORF_STOPS_STANDARD is
+ *              TAA TGA TAG, CNT_ORF_STARTS_ATG is ATG.  stops must not be 0; starts = 0: every run is reported whole.
+ *   frames     frame lane l in {0,1,2} holds the positions p = l (mod 3)
+ *   bounds     of a strand and a lane: l-3, every position of the lane that is a stop on that strand, and t_l, the one value
+ *              among len-2, len-1, len that is congruent to l: the two ends of the sequence act as stops for both strands
+ *   runs       each pair of consecutive bounds lo < hi is a stop-free run [lo+3, hi)
+ *   ORF of a run   starts == 0: the run.  starts != 0, forward: [a, hi) with a the smallest start position of the lane with
+ *              lo < a < hi; reverse: [lo+3, a+3) with a the largest such position.  A run that holds no start gives no ORF.
+ *   reported   iff its length is >= 3 and >= min_len.  The length is in nucleotides, a multiple of 3, and never includes the
+ *              stop codon.  min_len may be any value.
+ *   entry j    pos[j] = the lowest forward coordinate of the ORF, length[j] = its length, and, when info is not NULL,
+ *              info[j] = frame | CNT_FIND_REVERSE (reverse strand) | CNT_ORF_OPEN_END | CNT_ORF_NO_STOP
+ *                frame = pos % 3 on the forward strand, (len - pos - length) % 3 on the reverse strand: the frame numbers of
+ *                        cnt_translate's six frames
+ *                the opening bound is lo forward and hi reverse, the closing bound is the other one; CNT_ORF_OPEN_END is set
+ *                        when the opening bound is l-3 or t_l, CNT_ORF_NO_STOP when the closing bound is
+ *              cnt_translate(bits, len, pos[j], length[j], reverse ? CNT_TRANSLATE_REVCOMP : 0, ...) is the ORF's protein, and
+ *              cnt_extract accepts pos and info as they are
+ *   order      by hi ascending, forward before reverse at equal hi.  hi is the upper end of the untrimmed run, so trimming to
+ *              a start does not move an entry; with starts == 0 this is pos + length ascending.
+ *   n <= len per strand.  Input bits beyond len are ignored.  Nested or alternative starts inside an ORF are not reported.
+ * The checks, in this order and all before any device work:
+ *   1. stops == 0 or an unknown flag: CNT_EINVAL, even without work
+ *   2. len < 3 (no codon): CNT_OK with the count set to 0 (when a count pointer is given)
+ *   3. a NULL or not 8-B aligned bits, pos, length or count, an info not 8-B aligned, pos, length or info overlapping the input
+ *      words or each other; d_work NULL or work_bytes below the query's answer: CNT_EINVAL
+ * cnt_orfs_work_bytes: the device scratch cnt_orfs_dev needs; it depends on len only (0 when len < 3; d_work may then be
+ *   NULL), about 125 B per 8192 nt.
+ * Device tier: enqueue-only (no allocation, no synchronisation, capturable in a graph), d_bits at any 8-B phase, len up to
+ *   2^36, d_work any caller scratch that nobody needs zeroed.  *d_count (device u64) is SET to n; entries j < min(n, out_cap)
+ *   are written and nothing at or past out_cap: a caller whose buffers were too small reads n and calls again.
+ *   The previous stop of a lane can lie any number of tiles back, so it is carried by a scan and never walked to: per (strand,
+ *   lane) pair the value of a range is (its last stop, the start an ORF opening behind that stop would take), and two ranges
+ *   combine associatively.  Tiles of 8192 positions, one word and two look-ahead nucleotides per lane; the four sets are a
+ *   64-entry table in LDS.  Five passes: a value per tile and pair (orf_summary), one workgroup per pair that turns them into
+ *   each tile's carry-in (orf_carry), a count per tile (orf_count), the minimizers' offset scan, and the write pass, which
+ *   skips the tiles that emit nothing, repeats the count pass on the others and stores the entries at their offsets.
+ *   Measured on one MI355X, 2026-10-18, product build (DESIGN.md 4 "ORF scan", profiles/orfs_bench.jsonl): 2^30 nt of random
+ *   ACGT, standard stops, ATG starts, both strands at min_len 300 take 2.523 ms (one strand 1.761 ms; min_len 0: 2.956 ms with
+ *   25164003 entries), beside the six cnt_translate_dev calls of the whole sequence at 0.662 ms in the same run: 3.81x the six
+ *   translations' time.  rocprofv3 --kernel-trace --stats of three both-strand scans at min_len 300 of each bench input
+ *   splits a call into orf_summary 447.2 us, orf_carry 404.8 us, orf_count 716.5 us, minimizer_scan 19.7 us and orf_write
+ *   702.8 us on average: orf_count is the longest pass, and what bounds it was not isolated (no counters were collected).
+ * Host tier: synchronous; pinned bits, pos, length and info are used in place.  *count = n always; when n > out_cap the first
+ *   out_cap entries are written and the call returns CNT_ECAP. */
+#define CNT_ORF_BOTH_STRANDS 0x200u
+#define CNT_ORF_OPEN_END 0x400u /* in info[j]: the ORF's opening bound is the end of the sequence, not a stop codon */
+#define CNT_ORF_NO_STOP 0x800u  /* in info[j]: the ORF's closing bound is the end of the sequence, not a stop codon */
+#define CNT_ORF_STOPS_STANDARD ((1ull << 2) | (1ull << 14) | (1ull << 50)) /* TAA TGA TAG */
+#define CNT_ORF_STARTS_ATG (1ull << 56)
+int cnt_orfs_work_bytes(size_t len, size_t *bytes);
+int cnt_orfs_dev(const void *d_bits, size_t len, uint64_t stops, uint64_t starts, size_t min_len, unsigned flags, void *d_pos,
+                 void *d_length, void *d_info, size_t out_cap, void *d_count, void *d_work, size_t work_bytes, void *stream);
+int cnt_orfs(const uint64_t *bits, size_t len, uint64_t stops, uint64_t starts, size_t min_len, unsigned flags, uint64_t *pos,
+             uint64_t *length, uint64_t *info, size_t out_cap, uint64_t *count);
+
 /* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
  *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m
  *   h_i   = fmix64(x_i), the splitmix64 finaliser mod 2^64: z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9,

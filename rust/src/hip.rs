@@ -80,6 +80,9 @@ extern "C" {
     fn cnt_extract(bits: *const u64, len: usize, start: *const u64, info: *const u64, n: usize, region_len: usize, flags: c_uint, out: *mut u64, out_words: usize, rejected: *mut u64) -> c_int;
     fn cnt_translate_dev(d_bits: *const c_void, len: usize, start: usize, sub_len: usize, flags: c_uint, table: *const u8, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
     fn cnt_translate(bits: *const u64, len: usize, start: usize, sub_len: usize, flags: c_uint, table: *const u8, out: *mut u8, out_cap: usize) -> c_int;
+    fn cnt_orfs_work_bytes(len: usize, bytes: *mut usize) -> c_int;
+    fn cnt_orfs_dev(d_bits: *const c_void, len: usize, stops: u64, starts: u64, min_len: usize, flags: c_uint, d_pos: *mut c_void, d_length: *mut c_void, d_info: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_orfs(bits: *const u64, len: usize, stops: u64, starts: u64, min_len: usize, flags: c_uint, pos: *mut u64, length: *mut u64, info: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -665,6 +668,51 @@ pub fn translate_hip(bits: &[u64], len: usize, start: usize, sub_len: usize, rev
     out
 }
 
+const CNT_ORF_BOTH_STRANDS: c_uint = 0x200;
+/// In `info` of `orfs_hip`: the ORF's opening bound is the end of the sequence, not a stop codon.
+pub const ORF_OPEN_END: u64 = 0x400;
+/// In `info` of `orfs_hip`: the ORF's closing bound is the end of the sequence, not a stop codon.
+pub const ORF_NO_STOP: u64 = 0x800;
+/// The set of the standard stop codons TAA, TGA, TAG: bit `x0 | x1 << 2 | x2 << 4` of the codes A0 C1 T2 G3.
+pub const ORF_STOPS_STANDARD: u64 = (1u64 << 2) | (1u64 << 14) | (1u64 << 50);
+/// The set that holds ATG alone.
+pub const ORF_STARTS_ATG: u64 = 1u64 << 56;
+
+/// The open reading frames of the sequence as `(pos, length, info)`: the stop-free runs of each frame lane, on the forward strand
+/// or (`both_strands`) on both, trimmed to their first start codon (`starts == 0`: reported whole), at least `min_len`
+/// nucleotides long, ordered by the upper end of the run, forward before reverse.  `stops` and `starts` are 64-bit sets of codon
+/// values.  `info` is the frame plus `FIND_REVERSE`, `ORF_OPEN_END` and `ORF_NO_STOP`: `translate_hip(bits, len, pos, length,
+/// reverse, None)` is the protein, and `extract_hip` takes `pos` and `info` as they are.  Panics when `stops` is empty.
+pub fn orfs_hip(bits: &[u64], len: usize, stops: u64, starts: u64, min_len: usize, both_strands: bool) -> (Vec<u64>, Vec<u64>, Vec<u64>) {
+    need(bits, len);
+    if stops == 0 {
+        panic!("stops must hold at least one codon");
+    }
+    let most = if len < 3 { 0 } else if both_strands { 2 * len } else { len };
+    // random sequence: a stop every ~21 codons of a lane; a longer result is fetched again at its reported size
+    let mut cap = std::cmp::min(most, most / 16 + 1024);
+    let mut pos: Vec<u64> = Vec::with_capacity(cap);
+    let mut length: Vec<u64> = Vec::with_capacity(cap);
+    let mut info: Vec<u64> = Vec::with_capacity(cap);
+    let flags = if both_strands { CNT_ORF_BOTH_STRANDS } else { 0 };
+    let mut n: u64 = 0;
+    unsafe {
+        let fits = cnt_orfs(bits.as_ptr(), len, stops, starts, min_len, flags, pos.as_mut_ptr(), length.as_mut_ptr(), info.as_mut_ptr(), cap, &mut n) == 0;
+        if !fits {
+            // CNT_ECAP left the count in n; any other status comes back from the second call and panics in check
+            cap = n as usize;
+            pos = Vec::with_capacity(cap);
+            length = Vec::with_capacity(cap);
+            info = Vec::with_capacity(cap);
+            check(cnt_orfs(bits.as_ptr(), len, stops, starts, min_len, flags, pos.as_mut_ptr(), length.as_mut_ptr(), info.as_mut_ptr(), cap, &mut n));
+        }
+        pos.set_len(n as usize);
+        length.set_len(n as usize);
+        info.set_len(n as usize);
+    }
+    (pos, length, info)
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -871,6 +919,36 @@ pub fn translate_hip_dev(d_bits: &DeviceBuffer, len: usize, start: usize, sub_le
     }
     let flags = if revcomp { CNT_TRANSLATE_REVCOMP } else { 0 };
     unsafe { check(cnt_translate_dev(d_bits.ptr, len, start, sub_len, flags, table_ptr(table), d_out.ptr, d_out.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `orfs_hip_dev` needs for a sequence of `len` nucleotides (0 below 3).
+pub fn orfs_work_bytes(len: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_orfs_work_bytes(len, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the ORF scan of `len` device-resident nucleotides (see `orfs_hip`): `d_count` (one u64) is SET to the number of
+/// entries n, the first min(n, capacity) go to `d_pos`, `d_length` and, when given, `d_info`; `d_work` holds at least
+/// `orfs_work_bytes` bytes of any contents.
+pub fn orfs_hip_dev(d_bits: &DeviceBuffer, len: usize, stops: u64, starts: u64, min_len: usize, both_strands: bool, d_pos: &DeviceBuffer, d_length: &DeviceBuffer, d_info: Option<&DeviceBuffer>, d_count: &DeviceBuffer, d_work: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    if stops == 0 {
+        panic!("stops must hold at least one codon");
+    }
+    let flags = if both_strands { CNT_ORF_BOTH_STRANDS } else { 0 };
+    let both = std::cmp::min(d_pos.bytes, d_length.bytes);
+    let cap = match d_info {
+        Some(v) => std::cmp::min(both, v.bytes) / 8,
+        None => both / 8,
+    };
+    let info_ptr = match d_info {
+        Some(v) => v.ptr,
+        None => std::ptr::null_mut(),
+    };
+    unsafe { check(cnt_orfs_dev(d_bits.ptr, len, stops, starts, min_len, flags, d_pos.ptr, d_length.ptr, info_ptr, cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
