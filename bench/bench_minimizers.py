@@ -52,7 +52,7 @@ def launches(fn):
     with profile(activities=[ProfilerActivity.CUDA]) as prof:
         fn()
         torch.cuda.synchronize()
-    n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "minimizer" in e.name)
+    n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and ("minimizer" in e.name or "counted_scan" in e.name))
     return n or None
 
 

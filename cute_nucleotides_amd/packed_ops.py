@@ -105,6 +105,21 @@ def _n_windows(length, k, w):
     return m - w + 1 if m >= w else 0
 
 
+def _counted_hip(fn, cap, n_out, last, *args):
+    """The host tier of a call whose output size depends on the data: fn(*args, outputs..., cap, &n) with n_out uint64 outputs of
+    `cap` entries, the last one absent (NULL, returned as None) unless `last`.  A guess of cap that was short (CNT_ECAP) is
+    replaced once by the n the call reported.  Returns the [:n] views."""
+    for attempt in range(2):
+        outs = [np.empty(cap, dtype=np.uint64) if last or j < n_out - 1 else None for j in range(n_out)]
+        n = ctypes.c_uint64(0)
+        rc = fn(*args, *(_p(o) if o is not None else None for o in outs), cap, ctypes.byref(n))
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            cap = n.value
+            continue
+        check(rc)
+        return tuple(o[: n.value] if o is not None else None for o in outs)
+
+
 def minimizers_hip(bits, length, k, w, canonical=False, values=True):
     """The (w,k)-minimizers of the sequence (include/cute_nt.h "k-mers"): in each window of w consecutive k-mers the
     position with the smallest (fmix64(k-mer), position), each distinct position once, ascending.  Returns numpy uint64
@@ -113,17 +128,7 @@ def minimizers_hip(bits, length, k, w, canonical=False, values=True):
     bits = _packed(bits, length)
     n_win = _n_windows(length, k, w)
     cap = min(n_win, 2 * n_win // (w + 1) + n_win // 16 + 64)  # a random sequence selects ~2/(w+1) of its windows
-    flags = CNT_KMER_CANONICAL if canonical else 0
-    for attempt in range(2):
-        pos = np.empty(cap, dtype=np.uint64)
-        val = np.empty(cap, dtype=np.uint64) if values else None
-        n = ctypes.c_uint64(0)
-        rc = lib().cnt_minimizers(_p(bits), length, k, w, flags, _p(pos), _p(val) if values else None, cap, ctypes.byref(n))
-        if rc == _lib.CNT_ECAP and attempt == 0:
-            cap = n.value
-            continue
-        check(rc)
-        return pos[: n.value], (val[: n.value] if values else None)
+    return _counted_hip(lib().cnt_minimizers, cap, 2, values, _p(bits), length, k, w, CNT_KMER_CANONICAL if canonical else 0)
 
 
 _PATTERN_CODES = {"A": 0, "C": 1, "T": 2, "U": 2, "G": 3}
@@ -173,17 +178,7 @@ def find_pattern_hip(bits, length, pattern, max_mismatches=0, both_strands=False
     m = _n_kmers(length, k)
     most = 2 * m if both_strands else m
     cap = min(most, most // 1024 + 1024)  # a real search reports a handful of sites
-    flags = CNT_FIND_BOTH_STRANDS if both_strands else 0
-    for attempt in range(2):
-        pos = np.empty(cap, dtype=np.uint64)
-        inf = np.empty(cap, dtype=np.uint64) if info else None
-        n = ctypes.c_uint64(0)
-        rc = lib().cnt_find_pattern(_p(bits), length, p, k, wild, max_mismatches, flags, _p(pos), _p(inf) if info else None, cap, ctypes.byref(n))
-        if rc == _lib.CNT_ECAP and attempt == 0:
-            cap = n.value
-            continue
-        check(rc)
-        return pos[: n.value], (inf[: n.value] if info else None)
+    return _counted_hip(lib().cnt_find_pattern, cap, 2, info, _p(bits), length, p, k, wild, max_mismatches, CNT_FIND_BOTH_STRANDS if both_strands else 0)
 
 
 def _subseq_bounds(length, start, sub_len):
@@ -365,18 +360,7 @@ def orfs_hip(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_A
     bits = _packed(bits, length)
     most = (2 * length if both_strands else length) if length >= 3 else 0
     cap = min(most, most // 16 + 1024)  # random sequence: a stop every ~21 codons of a lane
-    flags = CNT_ORF_BOTH_STRANDS if both_strands else 0
-    for attempt in range(2):
-        pos = np.empty(cap, dtype=np.uint64)
-        lens = np.empty(cap, dtype=np.uint64)
-        inf = np.empty(cap, dtype=np.uint64) if info else None
-        n = ctypes.c_uint64(0)
-        rc = lib().cnt_orfs(_p(bits), length, stops, starts, min_len, flags, _p(pos), _p(lens), _p(inf) if info else None, cap, ctypes.byref(n))
-        if rc == _lib.CNT_ECAP and attempt == 0:
-            cap = n.value
-            continue
-        check(rc)
-        return pos[: n.value], lens[: n.value], (inf[: n.value] if info else None)
+    return _counted_hip(lib().cnt_orfs, cap, 3, info, _p(bits), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0)
 
 
 def validate_hip(n, allow_n=False):
@@ -441,11 +425,41 @@ def kmer_counts_dev(bits, length, k, canonical=False, out=None):
     return out[:bins]
 
 
+def _work_bytes(fn, *args):
+    out = ctypes.c_size_t(0)
+    check(fn(*args, ctypes.byref(out)))
+    return out.value
+
+
+def _counted_dev(torch, bits, most, pos, others, count, work, need):
+    """The device tier's common part of a call whose output size depends on the data.  `pos` is the caller's (any capacity: the
+    first min(n, capacity) entries are written) or None for `most` entries; each of `others` is None for a fresh tensor, False
+    for an output that is not written, the caller's tensor (at least as long as pos), or an exception to raise in its turn.
+    `count` and `work` (>= need bytes) are the caller's or None.  Returns (pos, others, count, ptrs): the tensors (None where
+    not written) and the trailing arguments of the _dev entry point from pos to work_bytes."""
+    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(most, 1), dtype=torch.int64, device=bits.device)
+    outs = []
+    for t in others:
+        if isinstance(t, Exception):
+            raise t
+        if t is False:
+            outs.append(None)
+        else:
+            outs.append(_out_words(torch, t, pos.numel(), bits) if t is not None else torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device))
+    count = _out_words(torch, count, 1, bits)
+    if work is None:
+        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
+    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
+        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
+    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    ptrs = [ctypes.c_void_p(t.data_ptr() or count.data_ptr()) if t is not None else None for t in [pos] + outs]
+    ptrs += [pos.numel(), ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size()]
+    return pos, outs, count, ptrs
+
+
 def minimizers_work_bytes(length, k, w):
     """bytes of device scratch cnt_minimizers_dev needs for this call (0 when there is no window)"""
-    out = ctypes.c_size_t(0)
-    check(lib().cnt_minimizers_work_bytes(length, k, w, ctypes.byref(out)))
-    return out.value
+    return _work_bytes(lib().cnt_minimizers_work_bytes, length, k, w)
 
 
 def minimizers_dev(bits, length, k, w, canonical=False, values=True, pos=None, val=None, work=None, count=None):
@@ -457,31 +471,21 @@ def minimizers_dev(bits, length, k, w, canonical=False, values=True, pos=None, v
     torch = _packed_dev(bits, length)
     n_win = _n_windows(length, k, w)
     # a given pos / val may hold fewer than W entries (the first min(n, capacity) are written); val at least as many as pos
-    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(n_win, 1), dtype=torch.int64, device=bits.device)
-    if values:
-        val = _out_words(torch, val, pos.numel(), bits) if val is not None else torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
-    elif val is not None:
-        raise ValueError("val given with values=False")
-    count = _out_words(torch, count, 1, bits)
-    need = minimizers_work_bytes(length, k, w)
-    if work is None:
-        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
-    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
-        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
-    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
-    pos_p = pos.data_ptr() or count.data_ptr()
-    val_p = (val.data_ptr() or count.data_ptr()) if values else None
-    _enqueue(bits, lib().cnt_minimizers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, w, CNT_KMER_CANONICAL if canonical else 0,
-             ctypes.c_void_p(pos_p), ctypes.c_void_p(val_p) if values else None, pos.numel(),
-             ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
-    return pos, (val if values else None), count
+    if not values:
+        val = ValueError("val given with values=False") if val is not None else False
+    pos, (val,), count, ptrs = _counted_dev(torch, bits, n_win, pos, [val], count, work, minimizers_work_bytes(length, k, w))
+    _enqueue(bits, lib().cnt_minimizers_dev, ctypes.c_void_p(bits.data_ptr()), length, k, w, CNT_KMER_CANONICAL if canonical else 0, *ptrs)
+    return pos, val, count
+
+
+def _info_arg(info):
+    """info=True|False|tensor of find_pattern_dev and orfs_dev as _counted_dev takes it"""
+    return None if info is True else False if info is False or info is None else info
 
 
 def find_pattern_work_bytes(length, k):
     """bytes of device scratch cnt_find_pattern_dev needs for this call (0 when there is no window)"""
-    out = ctypes.c_size_t(0)
-    check(lib().cnt_find_pattern_work_bytes(length, k, ctypes.byref(out)))
-    return out.value
+    return _work_bytes(lib().cnt_find_pattern_work_bytes, length, k)
 
 
 def find_pattern_dev(bits, length, pattern, max_mismatches=0, both_strands=False, info=True, pos=None, work=None, count=None):
@@ -495,26 +499,10 @@ def find_pattern_dev(bits, length, pattern, max_mismatches=0, both_strands=False
     torch = _packed_dev(bits, length)
     m = _n_kmers(length, k)
     most = 2 * m if both_strands else m
-    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(most, 1), dtype=torch.int64, device=bits.device)
-    if info is True:
-        inf = torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
-    elif info is False or info is None:
-        info = False
-    else:
-        inf, info = _out_words(torch, info, pos.numel(), bits), True
-    count = _out_words(torch, count, 1, bits)
-    need = find_pattern_work_bytes(length, k)
-    if work is None:
-        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
-    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
-        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
-    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
-    pos_p = pos.data_ptr() or count.data_ptr()
-    inf_p = (inf.data_ptr() or count.data_ptr()) if info else None
+    pos, (inf,), count, ptrs = _counted_dev(torch, bits, most, pos, [_info_arg(info)], count, work, find_pattern_work_bytes(length, k))
     _enqueue(bits, lib().cnt_find_pattern_dev, ctypes.c_void_p(bits.data_ptr()), length, p, k, wild, max_mismatches,
-             CNT_FIND_BOTH_STRANDS if both_strands else 0, ctypes.c_void_p(pos_p), ctypes.c_void_p(inf_p) if info else None, pos.numel(),
-             ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
-    return pos, (inf if info else None), count
+             CNT_FIND_BOTH_STRANDS if both_strands else 0, *ptrs)
+    return pos, inf, count
 
 
 def subseq_dev(bits, length, start, sub_len, revcomp=False, out=None):
@@ -584,9 +572,7 @@ def six_frames_dev(bits, length, table=None):
 
 def orfs_work_bytes(length):
     """bytes of device scratch cnt_orfs_dev needs for a sequence of this length (0 below 3 nucleotides)"""
-    out = ctypes.c_size_t(0)
-    check(lib().cnt_orfs_work_bytes(length, ctypes.byref(out)))
-    return out.value
+    return _work_bytes(lib().cnt_orfs_work_bytes, length)
 
 
 def orfs_dev(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_ATG, min_len=0, both_strands=False, info=True, pos=None, lens=None,
@@ -600,28 +586,9 @@ def orfs_dev(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_A
     stops, starts, min_len = _orf_args(stops, starts, min_len)
     torch = _packed_dev(bits, length)
     most = (2 * length if both_strands else length) if length >= 3 else 0
-    pos = _out_words(torch, pos, 0, bits) if pos is not None else torch.empty(max(most, 1), dtype=torch.int64, device=bits.device)
-    lens = _out_words(torch, lens, pos.numel(), bits) if lens is not None else torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
-    if info is True:
-        inf = torch.empty(max(pos.numel(), 1), dtype=torch.int64, device=bits.device)
-    elif info is False or info is None:
-        info = False
-    else:
-        inf, info = _out_words(torch, info, pos.numel(), bits), True
-    count = _out_words(torch, count, 1, bits)
-    need = orfs_work_bytes(length)
-    if work is None:
-        work = torch.empty(max(need, 1), dtype=torch.uint8, device=bits.device)
-    elif not work.is_cuda or not work.is_contiguous() or work.device != bits.device or work.numel() * work.element_size() < need:
-        raise ValueError("work must be a contiguous CUDA tensor on the input's device with >= %d bytes" % need)
-    # an empty view has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
-    pos_p = pos.data_ptr() or count.data_ptr()
-    len_p = lens.data_ptr() or count.data_ptr()
-    inf_p = (inf.data_ptr() or count.data_ptr()) if info else None
-    _enqueue(bits, lib().cnt_orfs_dev, ctypes.c_void_p(bits.data_ptr()), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0,
-             ctypes.c_void_p(pos_p), ctypes.c_void_p(len_p), ctypes.c_void_p(inf_p) if info else None, pos.numel(),
-             ctypes.c_void_p(count.data_ptr()), ctypes.c_void_p(work.data_ptr()), work.numel() * work.element_size())
-    return pos, lens, (inf if info else None), count
+    pos, (lens, inf), count, ptrs = _counted_dev(torch, bits, most, pos, [lens, _info_arg(info)], count, work, orfs_work_bytes(length))
+    _enqueue(bits, lib().cnt_orfs_dev, ctypes.c_void_p(bits.data_ptr()), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0, *ptrs)
+    return pos, lens, inf, count
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -24,6 +24,8 @@
 //   extract_abi.inc     region extraction: subsequences and windows
 //   translate_abi.inc   codon translation, any frame, either strand
 //   orf_abi.inc         open-reading-frame scan, one strand or both
+// counted_output.hpp (under the minimizers, pattern search and the ORF scan) holds the host helpers of the calls whose output
+// size depends on the data, on top of host_call.
 #include "../include/cute_nt.h"
 
 #include <hip/hip_runtime.h>

@@ -1,7 +1,8 @@
 // find_abi.inc -- C-ABI entry points of approximate pattern search (include/cute_nt.h, "pattern search"): the scratch query
 // cnt_find_pattern_work_bytes, cnt_find_pattern_dev (enqueue-only on a caller stream: three kernels, no allocation, no
 // synchronisation, capturable in a graph) and cnt_find_pattern (host tier: cute_nt.hip's host_call, staged through DevCtx::d_aux,
-// or in place when the caller's input and outputs are pinned).  Included at the end of cute_nt.hip, behind minimizer_abi.inc.
+// or in place when the caller's input and outputs are pinned).  The scratch layout, the scan, the common argument checks and the
+// host tier are counted_output.hpp's.  Included at the end of cute_nt.hip, behind minimizer_abi.inc.
 #include "find_kernels.hpp"
 
 namespace {
@@ -10,13 +11,8 @@ static_assert(CNT_FIND_REVERSE == kFindReverse, "the header's constant is the ke
 
 uint64_t find_windows(size_t len, unsigned k) { return len >= k ? (uint64_t)len - k + 1 : 0; }
 
-// scratch, the minimizers' layout (minimizer_scan is shared): from d_work aligned up to 16 B offs, one u64 per group of
-// kMinGroup tiles (an even number of them), then counts, one u32 per tile of whole groups
-uint64_t find_work_bytes(uint64_t m) {
-    if (!m) return 0;
-    const uint64_t groups = ((m + kFindTile - 1) / kFindTile + kMinGroup - 1) / kMinGroup;
-    return 16 + ((groups + 1) & ~1ull) * 8 + groups * kMinGroup * 4;
-}
+// scratch: the counted output's (counted_output.hpp), one tile per kFindTile windows
+uint64_t find_work_bytes(uint64_t m) { return counted_scratch_bytes((m + kFindTile - 1) / kFindTile); }
 
 // bit 2j set for every set bit j < 32 of x
 uint64_t find_spread(uint32_t x) {
@@ -45,12 +41,7 @@ int find_args(const void* bits, size_t len, uint64_t pattern, unsigned k, uint32
     *m = find_windows(len, k);
     *most = (flags & CNT_FIND_BOTH_STRANDS) ? 2 * *m : *m;
     if (*m == 0) return CNT_OK;
-    if (!bits || !pos || !count || !aligned(bits, 8) || !aligned(pos, 8) || !aligned(count, 8) || (info && !aligned(info, 8)))
-        return CNT_EINVAL;
-    const size_t in_bytes = cnt_words_for(len) * 8, out_bytes = std::min<uint64_t>(*most, out_cap) * 8;
-    if (overlaps(bits, in_bytes, pos, out_bytes) || (info && (overlaps(bits, in_bytes, info, out_bytes) || overlaps(pos, out_bytes, info, out_bytes))))
-        return CNT_EINVAL;
-    return CNT_OK;
+    return counted_args(bits, len, {{pos, true}, {info, false}}, *most, out_cap, count);
 }
 
 }  // namespace
@@ -68,15 +59,13 @@ int cnt_find_pattern_dev(const void* d_bits, size_t len, uint64_t pattern, unsig
     uint64_t m = 0, most = 0;
     CNT_TRY(find_args(d_bits, len, pattern, k, wildcards, max_mismatches, flags, d_pos, d_info, out_cap, d_count, &m, &most));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (m == 0) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;
+    if (m == 0) return counted_empty_dev(d_count, s);
     if (work_bytes < find_work_bytes(m) || !d_work) return CNT_EINVAL;
-    const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;
-    uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));
+    const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile;
+    const CountedScratch work = counted_carve(d_work, n_tiles);
     const uint8_t* in = static_cast<const uint8_t*>(d_bits);
     uint64_t* pos = static_cast<uint64_t*>(d_pos);
     uint64_t* info = static_cast<uint64_t*>(d_info);
-    uint64_t* count = static_cast<uint64_t*>(d_count);
     const uint32_t used = k < 32 ? (1u << k) - 1u : ~0u, care = ~wildcards & used;
     uint32_t rcare = 0;  // wildcards' bit j = wildcards bit k-1-j
     for (unsigned j = 0; j < k; ++j) rcare |= ((care >> (k - 1 - j)) & 1u) << j;
@@ -87,11 +76,11 @@ int cnt_find_pattern_dev(const void* d_bits, size_t len, uint64_t pattern, unsig
     static const FindKernel kWrite[4] = {find_write_k16, find_write_k16_both, find_write_k32, find_write_k32_both};
     const int which = (wide ? 2 : 0) + (both ? 1 : 0);
     split_launches(n_tiles, kFindBlock, [&](uint64_t t, uint64_t n) {
-        hipLaunchKernelGGL(kCount[which], dim3((unsigned)n), dim3(kFindBlock), 0, s, in, words, m, p, t, counts, offs, pos, info, (uint64_t)out_cap);
+        hipLaunchKernelGGL(kCount[which], dim3((unsigned)n), dim3(kFindBlock), 0, s, in, words, m, p, t, work.counts, work.offs, pos, info, (uint64_t)out_cap);
     });
-    hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);
+    counted_scan_enqueue(work, n_tiles, d_count, s);
     split_launches(n_tiles, kFindBlock, [&](uint64_t t, uint64_t n) {
-        hipLaunchKernelGGL(kWrite[which], dim3((unsigned)n), dim3(kFindBlock), 0, s, in, words, m, p, t, counts, offs, pos, info, (uint64_t)out_cap);
+        hipLaunchKernelGGL(kWrite[which], dim3((unsigned)n), dim3(kFindBlock), 0, s, in, words, m, p, t, work.counts, work.offs, pos, info, (uint64_t)out_cap);
     });
     return hip_rc(hipGetLastError());
 }
@@ -100,20 +89,13 @@ int cnt_find_pattern(const uint64_t* bits, size_t len, uint64_t pattern, unsigne
                      uint64_t* pos, uint64_t* info, size_t out_cap, uint64_t* count) {
     uint64_t m = 0, most = 0;
     CNT_TRY(find_args(bits, len, pattern, k, wildcards, max_mismatches, flags, pos, info, out_cap, count, &m, &most));
-    if (m == 0) {
-        if (count) *count = 0;
-        return CNT_OK;
-    }
-    // the pinned lane needs cap > 0: an empty pos is never pinned
-    const size_t cap = std::min<uint64_t>(most, out_cap), work_bytes = find_work_bytes(m);
-    uint64_t n = 0;
-    CNT_TRY(host_call({{bits, cnt_words_for(len) * 8, Dir::in}, {pos, cap * 8, Dir::counted}, {info, cap * 8, Dir::counted}}, 8 + work_bytes, &n,
-                      false, [&](void* const* d, void* aux, hipStream_t s) {  // aux: the device count, then the scratch
-                          return cnt_find_pattern_dev(d[0], len, pattern, k, wildcards, max_mismatches, flags, d[1], d[2], cap, aux,
-                                                      static_cast<uint8_t*>(aux) + 8, work_bytes, s);
-                      }));
-    *count = n;
-    return n > out_cap ? CNT_ECAP : CNT_OK;
+    if (m == 0) return counted_empty(count);
+    const size_t work_bytes = find_work_bytes(m);
+    return counted_host_call(bits, len, {pos, info}, most, out_cap, count, work_bytes,
+                             [&](void* const* d, size_t cap, void* d_count, void* d_work, hipStream_t s) {
+                                 return cnt_find_pattern_dev(d[0], len, pattern, k, wildcards, max_mismatches, flags, d[1], d[2], cap, d_count, d_work,
+                                                             work_bytes, s);
+                             });
 }
 
 }  // extern "C"

@@ -7,10 +7,10 @@
 // a compare.  The reverse strand needs no reverse complement of the text: window x hits the reverse strand iff x is within
 // max_mismatches of the pattern's reverse complement, so it is a second XOR against P' with care' on the same window.
 //
-// The output size depends on the data, so a call is the three kernels of the minimizers (minimizer_kernels.hpp), none of which
-// allocates, with the same scratch layout so that minimizer_scan serves as it is:
+// The output size depends on the data, so a call is the three passes of counted_output.hpp, which owns the scratch layout, none of
+// which allocates:
 //   1. find_count_*: one workgroup per tile of kFindTile windows counts the tile's hits into counts[tile];
-//   2. minimizer_scan: offs[group] = the exclusive offset of each group of kMinGroup tiles, *count SET to the total;
+//   2. counted_scan: offs[group] = the exclusive offset of each group of kCountedGroup tiles, *count SET to the total;
 //   3. find_write_*: a tile whose count is 0 returns at once (nearly every tile of a real search); the others are
 //      recomputed (0.25 B/nt: cheaper than staging candidates), a workgroup prefix sum over the lanes' hit counts places each
 //      lane's run, and the lane stores its hits in window order, forward before reverse, below out_cap only.
@@ -24,7 +24,7 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
-#include "minimizer_kernels.hpp"
+#include "counted_output.hpp"
 
 namespace cnt {
 
@@ -116,21 +116,10 @@ __device__ __forceinline__ void find_tile(const uint8_t* __restrict__ in, uint64
     fm &= valid;
     rm &= valid;
     const uint32_t c = (uint32_t)__popc(fm) + (uint32_t)__popc(rm);
-    uint32_t x = c;  // inclusive scan over the wave (lane order = window order)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= (uint32_t)o) x += y;
-    }
+    const uint32_t x = wave_inclusive_sum(c, lane);  // lane order = window order
     if (lane == 63) s_cnt[wave] = x;
     if constexpr (WRITE) {
-        if (j == 0) {
-            uint64_t b = offs[tile / kMinGroup];
-            const uint32_t* g = counts + (tile - tile % kMinGroup);
-#pragma unroll
-            for (int q = 0; q < kMinGroup - 1; ++q) b += (uint64_t)q < tile % kMinGroup ? g[q] : 0u;
-            s_base = b;
-        }
+        if (j == 0) s_base = counted_tile_base(offs, counts, tile);
     }
     __syncthreads();
     if constexpr (!WRITE) {

@@ -2,15 +2,11 @@
 // w consecutive k-mers the position with the smallest (fmix64(k-mer), position), output once per distinct position in
 // ascending order.  Not in the reference; the definition is restated in Python and numpy by tests/test_minimizers.py.
 //
-// The output size depends on the data, so a call is three kernels on one stream, none of which allocates:
+// The output size depends on the data, so a call is the three passes of counted_output.hpp, which owns the scratch layout:
 //   1. minimizer_tiles<false>: one workgroup per tile of kMinTile windows counts the tile's new positions into counts[tile];
-//   2. minimizer_scan: one workgroup sums the counts by groups of kMinGroup tiles (one 64-B read per lane), writes each
-//      group's exclusive offset to offs[group] and SETS *count to the total;
+//   2. counted_scan;
 //   3. minimizer_tiles<true>: the same tiles again, recomputed (the input is 0.25 B/nt: cheaper than staging candidates),
-//      store their positions (and k-mers) at offs[group] + the counts of the group's earlier tiles + their rank in the
-//      tile, below out_cap only.
-// A first scan of one u64 per tile, read and written by one lane per 16 consecutive tiles, took 0.52 ms of an 8.2-ms call
-// at 2^30 nt: its loads and stores were 64 cache lines per wave instruction.
+//      store their positions (and k-mers) at counted_tile_base() + their rank in the tile, below out_cap only.
 // A tile holds the windows t0-1 .. t0+T-1: the one extra window on the left makes "t is new iff p(t) != p(t-1)" local to
 // the tile.  It needs the T+w k-mers t0-1 .. t0+T+w-2; their hashes go to LDS, and log2(w) doubling steps turn them into
 // the minimum of 2^L consecutive (hash, position) pairs, 2^L the largest power of two <= w.  A window [s, s+w) is then
@@ -20,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "counted_output.hpp"
 #include "kmer_kernels.hpp"
 #include "util_kernels.hpp"
 
@@ -31,7 +28,6 @@ constexpr uint32_t kMinEntries = kMinTile + kMinMaxW;                  // k-mers
 constexpr int kMinRounds = (int)(kMinEntries / kMinBlock);             // entries per lane: e = r * BLOCK + lane
 constexpr int kMinWinRounds = (int)(kMinTile / kMinBlock);             // windows per lane: t = t0 + r * BLOCK + lane
 constexpr int kMinWaves = kMinBlock / 64;
-constexpr int kMinScanBlock = 1024, kMinGroup = 16;                    // the offset scan: one workgroup, a group of 16 tiles per lane
 static_assert(kMinEntries % kMinBlock == 0 && kMinTile % kMinBlock == 0 && kMinEntries < 65536, "local indices are u16");
 
 // k-mer i (i + k <= len) as cnt_kmers writes it: the funnel of kmer_tiles over words i>>5 and i>>5 + 1.  The second word is
@@ -136,11 +132,7 @@ __global__ __launch_bounds__(kMinBlock) void minimizer_tiles(const uint64_t* __r
             s_cnt[q] = c;
             c += x;
         }
-        uint64_t b = offs[tile / kMinGroup];
-        const uint32_t* g = counts + (tile - tile % kMinGroup);
-#pragma unroll
-        for (int q = 0; q < kMinGroup - 1; ++q) b += (uint64_t)q < tile % kMinGroup ? g[q] : 0u;
-        s_base = b;
+        s_base = counted_tile_base(offs, counts, tile);
     }
     __syncthreads();
     const uint64_t base = s_base;
@@ -155,48 +147,6 @@ __global__ __launch_bounds__(kMinBlock) void minimizer_tiles(const uint64_t* __r
         __builtin_nontemporal_store(i, pos + j);
         if (val) __builtin_nontemporal_store(minimizer_kmer(in, last_word, i, k, canon), val + j);
     }
-}
-
-// One workgroup; lane j of a pass sums the kMinGroup counts of group j (four 16-B loads: counts is 16-B aligned and holds
-// whole groups, the entries past n_tiles are ignored), offs[group] = the exclusive prefix; *count = the total (set, not added).
-__global__ __launch_bounds__(kMinScanBlock) void minimizer_scan(const uint32_t* __restrict__ counts, uint64_t* __restrict__ offs,
-                                                                uint64_t n_tiles, uint64_t* __restrict__ count) {
-    __shared__ uint64_t s_w[kMinScanBlock / 64];
-    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint64_t n_groups = (n_tiles + kMinGroup - 1) / kMinGroup;
-    uint64_t carry = 0;
-    for (uint64_t first = 0; first < n_groups; first += kMinScanBlock) {
-        const uint64_t g = first + threadIdx.x;
-        uint64_t sum = 0;
-        if (g < n_groups) {
-            const u32x4* q = reinterpret_cast<const u32x4*>(counts + g * kMinGroup);
-#pragma unroll
-            for (int u = 0; u < kMinGroup / 4; ++u) {
-                const u32x4 c = q[u];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) sum += g * kMinGroup + 4 * u + e < n_tiles ? c[e] : 0u;
-            }
-        }
-        uint64_t x = sum;  // inclusive scan over the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t lo = __shfl_up((uint32_t)x, o, 64), hi = __shfl_up((uint32_t)(x >> 32), o, 64);
-            if (lane >= (uint32_t)o) x += ((uint64_t)hi << 32) | lo;
-        }
-        if (lane == 63) s_w[wave] = x;
-        __syncthreads();
-        uint64_t before = carry + x - sum, total = 0;
-#pragma unroll
-        for (int q = 0; q < kMinScanBlock / 64; ++q) {
-            const uint64_t y = s_w[q];
-            before += q < (int)wave ? y : 0;
-            total += y;
-        }
-        if (g < n_groups) offs[g] = before;
-        carry += total;
-        __syncthreads();  // s_w is rewritten by the next pass
-    }
-    if (threadIdx.x == 0) *count = carry;
 }
 
 }  // namespace cnt

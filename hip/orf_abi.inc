@@ -1,7 +1,8 @@
 // orf_abi.inc -- C-ABI entry points of the open-reading-frame scan (include/cute_nt.h, "ORF scan"): the scratch query
 // cnt_orfs_work_bytes, cnt_orfs_dev (enqueue-only on a caller stream: five passes, no allocation, no synchronisation, capturable
 // in a graph) and cnt_orfs (host tier: cute_nt.hip's host_call, staged through DevCtx::d_aux, or in place when the caller's input
-// and outputs are pinned).  Included at the end of cute_nt.hip, behind translate_abi.inc.
+// and outputs are pinned).  The layout of counts and offs, the scan, the common argument checks and the host tier are
+// counted_output.hpp's.  Included at the end of cute_nt.hip, behind translate_abi.inc.
 #include "orf_kernels.hpp"
 
 namespace {
@@ -11,14 +12,9 @@ static_assert(CNT_ORF_OPEN_END == kOrfOpenEnd && CNT_ORF_NO_STOP == kOrfNoStop, 
 // the tiles of a call: the positions 0 .. len, the three closing bounds len-2 .. len among them
 uint64_t orf_tiles(size_t len) { return len < 3 ? 0 : (uint64_t)len / kOrfTile + 1; }
 
-// scratch: from d_work aligned up to 16 B the minimizers' layout (minimizer_scan is shared) -- offs, one u64 per group of kMinGroup
-// tiles (an even number of them), then counts, one u32 per tile of whole groups -- then sums, kOrfPairs u32 per tile, then carry,
-// 2 * kOrfPairs u64 per tile
-uint64_t orf_work_bytes(uint64_t n_tiles) {
-    if (!n_tiles) return 0;
-    const uint64_t groups = (n_tiles + kMinGroup - 1) / kMinGroup;
-    return 16 + ((groups + 1) & ~1ull) * 8 + groups * kMinGroup * 4 + n_tiles * kOrfPairs * (4 + 2 * 8);
-}
+// scratch: the counted output's (counted_output.hpp), and behind it sums, kOrfPairs u32 per tile, then carry, 2 * kOrfPairs u64
+// per tile
+uint64_t orf_work_bytes(uint64_t n_tiles) { return counted_scratch_bytes(n_tiles) + n_tiles * kOrfPairs * (4 + 2 * 8); }
 
 // the set whose test on c is the test of `set` on rc3(c): the outer codes swapped, all three complemented
 uint64_t orf_rc3(uint64_t set) {
@@ -34,14 +30,7 @@ int orf_args(const void* bits, size_t len, uint64_t stops, unsigned flags, const
     if (stops == 0 || (flags & ~CNT_ORF_BOTH_STRANDS)) return CNT_EINVAL;
     *most = (flags & CNT_ORF_BOTH_STRANDS) ? 2 * (uint64_t)len : len;
     if (len < 3) return CNT_OK;
-    if (!bits || !pos || !length || !count || !aligned(bits, 8) || !aligned(pos, 8) || !aligned(length, 8) || !aligned(count, 8) ||
-        (info && !aligned(info, 8)))
-        return CNT_EINVAL;
-    const size_t in_bytes = cnt_words_for(len) * 8, out_bytes = std::min<uint64_t>(*most, out_cap) * 8;
-    if (overlaps(bits, in_bytes, pos, out_bytes) || overlaps(bits, in_bytes, length, out_bytes) || overlaps(pos, out_bytes, length, out_bytes)) return CNT_EINVAL;
-    if (info && (overlaps(bits, in_bytes, info, out_bytes) || overlaps(pos, out_bytes, info, out_bytes) || overlaps(length, out_bytes, info, out_bytes)))
-        return CNT_EINVAL;
-    return CNT_OK;
+    return counted_args(bits, len, {{pos, true}, {length, true}, {info, false}}, *most, out_cap, count);
 }
 
 }  // namespace
@@ -59,12 +48,11 @@ int cnt_orfs_dev(const void* d_bits, size_t len, uint64_t stops, uint64_t starts
     uint64_t most = 0;
     CNT_TRY(orf_args(d_bits, len, stops, flags, d_pos, d_length, d_info, out_cap, d_count, &most));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (len < 3) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;
-    const uint64_t n_tiles = orf_tiles(len), groups = (n_tiles + kMinGroup - 1) / kMinGroup;
+    if (len < 3) return counted_empty_dev(d_count, s);
+    const uint64_t n_tiles = orf_tiles(len);
     if (work_bytes < orf_work_bytes(n_tiles) || !d_work) return CNT_EINVAL;
-    uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);
-    uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));
-    uint32_t* sums = counts + groups * kMinGroup;
+    const CountedScratch work = counted_carve(d_work, n_tiles);
+    uint32_t* sums = static_cast<uint32_t*>(work.behind);
     uint64_t* carry = reinterpret_cast<uint64_t*>(sums + n_tiles * kOrfPairs);
     const bool both = (flags & CNT_ORF_BOTH_STRANDS) != 0;
     const OrfArgs a = {static_cast<const uint8_t*>(d_bits),
@@ -76,8 +64,8 @@ int cnt_orfs_dev(const void* d_bits, size_t len, uint64_t stops, uint64_t starts
                        n_tiles,
                        sums,
                        carry,
-                       counts,
-                       offs,
+                       work.counts,
+                       work.offs,
                        static_cast<uint64_t*>(d_pos),
                        static_cast<uint64_t*>(d_length),
                        static_cast<uint64_t*>(d_info),
@@ -85,7 +73,7 @@ int cnt_orfs_dev(const void* d_bits, size_t len, uint64_t stops, uint64_t starts
     split_launches(n_tiles, kOrfBlock, [&](uint64_t t, uint64_t n) { hipLaunchKernelGGL(orf_summary, dim3((unsigned)n), dim3(kOrfBlock), 0, s, a, t); });
     hipLaunchKernelGGL(orf_carry, dim3(both ? kOrfPairs : 3), dim3(kOrfCarryBlock), 0, s, sums, carry, n_tiles);
     split_launches(n_tiles, kOrfBlock, [&](uint64_t t, uint64_t n) { hipLaunchKernelGGL(orf_count, dim3((unsigned)n), dim3(kOrfBlock), 0, s, a, t); });
-    hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, static_cast<uint64_t*>(d_count));
+    counted_scan_enqueue(work, n_tiles, d_count, s);
     split_launches(n_tiles, kOrfBlock, [&](uint64_t t, uint64_t n) { hipLaunchKernelGGL(orf_write, dim3((unsigned)n), dim3(kOrfBlock), 0, s, a, t); });
     return hip_rc(hipGetLastError());
 }
@@ -94,20 +82,12 @@ int cnt_orfs(const uint64_t* bits, size_t len, uint64_t stops, uint64_t starts, 
              uint64_t* info, size_t out_cap, uint64_t* count) {
     uint64_t most = 0;
     CNT_TRY(orf_args(bits, len, stops, flags, pos, length, info, out_cap, count, &most));
-    if (len < 3) {
-        if (count) *count = 0;
-        return CNT_OK;
-    }
-    // the pinned lane needs cap > 0: an empty pos is never pinned
-    const size_t cap = std::min<uint64_t>(most, out_cap), work_bytes = orf_work_bytes(orf_tiles(len));
-    uint64_t n = 0;
-    CNT_TRY(host_call({{bits, cnt_words_for(len) * 8, Dir::in}, {pos, cap * 8, Dir::counted}, {length, cap * 8, Dir::counted}, {info, cap * 8, Dir::counted}},
-                      8 + work_bytes, &n, false, [&](void* const* d, void* aux, hipStream_t s) {  // aux: the device count, then the scratch
-                          return cnt_orfs_dev(d[0], len, stops, starts, min_len, flags, d[1], d[2], d[3], cap, aux, static_cast<uint8_t*>(aux) + 8,
-                                              work_bytes, s);
-                      }));
-    *count = n;
-    return n > out_cap ? CNT_ECAP : CNT_OK;
+    if (len < 3) return counted_empty(count);
+    const size_t work_bytes = orf_work_bytes(orf_tiles(len));
+    return counted_host_call(bits, len, {pos, length, info}, most, out_cap, count, work_bytes,
+                             [&](void* const* d, size_t cap, void* d_count, void* d_work, hipStream_t s) {
+                                 return cnt_orfs_dev(d[0], len, stops, starts, min_len, flags, d[1], d[2], d[3], cap, d_count, d_work, work_bytes, s);
+                             });
 }
 
 }  // extern "C"

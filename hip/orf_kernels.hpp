@@ -13,12 +13,12 @@
 // across the 64 lanes of a wave (shuffles), across the four waves of a tile (LDS) and across tiles (orf_carry).  Inside a tile
 // a pair's value is one dword, stop + 1 - tile0 in the high half and start + 1 - tile0 in the low one, 0 = none.
 //
-// Passes (orf_abi.inc), none of which allocates; counts / offs have the minimizers' layout so that minimizer_scan serves as it is:
+// Passes (orf_abi.inc), none of which allocates; counts / offs and passes 3 to 5 are the counted output of counted_output.hpp:
 //   1. orf_summary   one workgroup per tile of kOrfTile positions: sums[pair][tile] = the tile's value of each pair;
 //   2. orf_carry     one workgroup per pair turns the tiles' values into carry[pair][tile], the value of everything in front of
 //                    the tile, in sequence coordinates (u64, ~0 = none);
 //   3. orf_count     counts[tile] = the entries the tile's bounds emit;
-//   4. minimizer_scan
+//   4. counted_scan
 //   5. orf_write     a tile whose count is 0 returns at once; the others repeat pass 3 and store their entries in order.
 // Shape of a tile, as in find_kernels.hpp: lane j owns the 32 positions that start in word j of the tile; it reads that word and
 // the next (two look-ahead nucleotides).  The four sets (stops and starts of either strand, the reverse ones already composed
@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
+#include "counted_output.hpp"
 #include "find_kernels.hpp"
 
 namespace cnt {
@@ -317,21 +318,10 @@ __device__ __forceinline__ void orf_tile(const OrfArgs& a, uint64_t first_tile) 
         }
     }
     const uint32_t c = (uint32_t)__popc(fm) + (uint32_t)__popc(rm);
-    uint32_t n = c;  // inclusive scan over the wave (lane order = position order)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(n, o, 64);
-        if (lane >= (uint32_t)o) n += y;
-    }
+    const uint32_t n = wave_inclusive_sum(c, lane);  // lane order = position order
     if (lane == 63) s_cnt[wave] = n;
     if constexpr (WRITE) {
-        if (j == 0) {
-            uint64_t b = a.offs[tile / kMinGroup];
-            const uint32_t* g = a.counts + (tile - tile % kMinGroup);
-#pragma unroll
-            for (int q = 0; q < kMinGroup - 1; ++q) b += (uint64_t)q < tile % kMinGroup ? g[q] : 0u;
-            s_base = b;
-        }
+        if (j == 0) s_base = counted_tile_base(a.offs, a.counts, tile);
     }
     __syncthreads();
     if constexpr (!WRITE) {

@@ -586,7 +586,7 @@ int cnt_translate(const uint64_t *bits, size_t len, size_t start, size_t sub_len
  *   25164003 entries), beside the six cnt_translate_dev calls of the whole sequence at 0.662 ms in the same run: 3.81x the six
  *   translations' time.  rocprofv3 --kernel-trace --stats of three both-strand scans at min_len 300 of each bench input
  *   splits a call into orf_summary 447.2 us, orf_carry 404.8 us, orf_count 716.5 us, minimizer_scan 19.7 us and orf_write
- *   702.8 us on average: orf_count is the longest pass, and what bounds it was not isolated (no counters were collected).
+ *   702.8 us on average (the scan kernel is now named counted_scan): orf_count is the longest pass, and what bounds it was not isolated (no counters were collected).
  * Host tier: synchronous; pinned bits, pos, length and info are used in place.  *count = n always; when n > out_cap the first
  *   out_cap entries are written and the call returns CNT_ECAP. */
 #define CNT_ORF_BOTH_STRANDS 0x200u

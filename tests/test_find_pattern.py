@@ -18,6 +18,7 @@ import pytest
 
 from test_gpu_multi_launch import launch_tiles  # noqa: F401 -- the fixture: the lab build at 64 / 128 tiles per launch
 from test_kmers import assert_split_launches_by_max_tiles_per_launch
+from test_minimizers import assert_counted_output_source
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CNT_FIND_BOTH_STRANDS = 0x20
@@ -433,12 +434,13 @@ def test_find_plan_matches_the_launcher_and_splitter_source():
     src = open(os.path.join(ROOT, "hip", "find_kernels.hpp")).read()
     assert "constexpr int kFindBlock = 256;" in src and "kFindTileWords = kFindBlock, kFindTile = 32 * kFindTileWords;" in src
     abi = open(os.path.join(ROOT, "hip", "find_abi.inc")).read()
-    scan = "hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);"
-    for line in ("const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;", scan,
-                 "if (m == 0) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;"):
+    scan = "counted_scan_enqueue(work, n_tiles, d_count, s);"
+    for line in ("const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile;", "const CountedScratch work = counted_carve(d_work, n_tiles);", scan,
+                 "if (m == 0) return counted_empty_dev(d_count, s);"):
         assert line in abi, line
+    assert_counted_output_source()
     tiles = "split_launches(n_tiles, kFindBlock, [&](uint64_t t, uint64_t n) {"
-    assert abi.count(tiles) == 2 and abi.count("minimizer_scan") == 2  # the launch and the comment on the shared layout
+    assert abi.count(tiles) == 2 and abi.count("counted_scan") == 1
     assert abi.index(tiles) < abi.index(scan) < abi.rindex(tiles)
     assert_split_launches_by_max_tiles_per_launch()
     assert FIND_HW_LAUNCH_TILES == 8388544

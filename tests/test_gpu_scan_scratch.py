@@ -7,7 +7,7 @@ the three queries, and tests the guard checker on synthetic buffers.  The GPU pa
 byte phases 0, 1, 7, 8 and 15 of a 16-B-aligned buffer, between two 256-B guards of 0xA5, once zeroed and once filled with 0xFF:
 the results equal the references both times, no byte outside the model's body changes, and the bytes that do change begin at the
 aligned base and end at the model's written extent -- the guards sit on the edges.  The last part puts stops, starts and hits at
-the edges of orf_carry (64 tiles to a wave, 1024 to a round) and of minimizer_scan (64 groups of 16 tiles to a wave) in one
+the edges of orf_carry (64 tiles to a wave, 1024 to a round) and of counted_scan (64 groups of 16 tiles to a wave) in one
 sequence of 1027 tiles.  Every comparison is exact; every reference is one of the suite's own."""
 import ctypes
 import os
@@ -23,35 +23,44 @@ from test_orfs import (ATG, ATG_CODES, CAT, CNT_FIND_REVERSE, CNT_ORF_BOTH_STRAN
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OPS = ("minimizers", "find", "orfs")
 TILE = {"minimizers": 2048, "find": 8192, "orfs": 8192}  # kMinTile windows, kFindTile windows, kOrfTile positions
-GROUP = 16      # kMinGroup: tiles per offset of the shared scan
+GROUP = 16      # kCountedGroup: tiles per offset of the shared scan
 ORF_PAIRS = 6   # kOrfPairs: (strand, lane)
 MIN_K, MIN_W = 15, 10
 FIND_K, FIND_D = 12, 4
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------
-# The carving, the same three lines in hip/minimizer_abi.inc, hip/find_abi.inc and hip/orf_abi.inc:
+# The carving, stated once, in hip/counted_output.hpp (counted_carve; `behind` is its third member):
+#     const uint64_t groups = (n_tiles + kCountedGroup - 1) / kCountedGroup;
 #     uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);
 #     uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));
-# and in hip/orf_abi.inc behind them
-#     uint32_t* sums = counts + groups * kMinGroup;
+#     return {offs, counts, counts + groups * kCountedGroup};
+# which hip/minimizer_abi.inc, hip/find_abi.inc and hip/orf_abi.inc each call on their own number of tiles, and in hip/orf_abi.inc
+# behind it
+#     uint32_t* sums = static_cast<uint32_t*>(work.behind);
 #     uint64_t* carry = reinterpret_cast<uint64_t*>(sums + n_tiles * kOrfPairs);
 # with carry holding 2 * kOrfPairs u64 per tile (hip/orf_kernels.hpp: "uint64_t* carry;  // [kOrfPairs][2][n_tiles]: stop, start").
+# The byte formula of the queries is there too (counted_scratch_bytes), and orf_abi.inc adds its own regions to it.
+CARVE_CALL = "const CountedScratch work = counted_carve(d_work, n_tiles);"
 CARVING = {
-    "minimizer_abi.inc": ["uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);",
-                          "uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));",
-                          "const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;"],
-    "find_abi.inc": ["uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);",
-                     "uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));",
-                     "const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;"],
-    "orf_abi.inc": ["uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);",
-                    "uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));",
-                    "uint32_t* sums = counts + groups * kMinGroup;",
+    "counted_output.hpp": ["constexpr int kCountedScanBlock = 1024, kCountedGroup = 16;",
+                           "const uint64_t groups = (n_tiles + kCountedGroup - 1) / kCountedGroup;",
+                           "uint64_t* offs = reinterpret_cast<uint64_t*>((reinterpret_cast<uintptr_t>(d_work) + 15) & ~(uintptr_t)15);",
+                           "uint32_t* counts = reinterpret_cast<uint32_t*>(offs + ((groups + 1) & ~1ull));",
+                           "return {offs, counts, counts + groups * kCountedGroup};",
+                           "if (!n_tiles) return 0;",
+                           "return 16 + ((groups + 1) & ~1ull) * 8 + groups * kCountedGroup * 4;"],
+    "minimizer_abi.inc": ["const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile;", CARVE_CALL,
+                          "uint64_t minimizer_work_bytes(uint64_t n_win) { return counted_scratch_bytes((n_win + kMinTile - 1) / kMinTile); }"],
+    "find_abi.inc": ["const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile;", CARVE_CALL,
+                     "uint64_t find_work_bytes(uint64_t m) { return counted_scratch_bytes((m + kFindTile - 1) / kFindTile); }"],
+    "orf_abi.inc": ["const uint64_t n_tiles = orf_tiles(len);", CARVE_CALL,
+                    "uint32_t* sums = static_cast<uint32_t*>(work.behind);",
                     "uint64_t* carry = reinterpret_cast<uint64_t*>(sums + n_tiles * kOrfPairs);",
-                    "const uint64_t n_tiles = orf_tiles(len), groups = (n_tiles + kMinGroup - 1) / kMinGroup;"],
+                    "uint64_t orf_work_bytes(uint64_t n_tiles) { return counted_scratch_bytes(n_tiles) + n_tiles * kOrfPairs * (4 + 2 * 8); }"],
 }
 # The stores into the scratch, all there are:
-#   offs[0 .. groups)        hip/minimizer_kernels.hpp minimizer_scan   "if (g < n_groups) offs[g] = before;"
+#   offs[0 .. groups)        hip/counted_output.hpp counted_scan        "if (g < n_groups) offs[g] = before;"
 #   counts[0 .. n_tiles)     hip/minimizer_kernels.hpp minimizer_tiles  "counts[tile] = (uint32_t)c;"
 #                            hip/find_kernels.hpp find_tile             "counts[tile] = total;"
 #                            hip/orf_kernels.hpp orf_tile               "a.counts[tile] = total;"
@@ -62,7 +71,8 @@ CARVING = {
 # every tile of a call runs its count pass and every group its scan lane, so a call that has finished HAS written all of these;
 # the odd offs slot, the counts of the tiles a last group lacks and, on one strand, pairs 3 .. 5 of sums and carry are never stored.
 STORES = {
-    "minimizer_kernels.hpp": ["if (g < n_groups) offs[g] = before;", "counts[tile] = (uint32_t)c;"],
+    "counted_output.hpp": ["if (g < n_groups) offs[g] = before;"],
+    "minimizer_kernels.hpp": ["counts[tile] = (uint32_t)c;"],
     "find_kernels.hpp": ["counts[tile] = total;"],
     "orf_kernels.hpp": ["a.counts[tile] = total;", "if (threadIdx.x < (both ? kOrfPairs : 3)) {", "a.sums[p * a.n_tiles + tile] = v;",
                         "uint64_t* out_stop = carry + 2ull * p * n_tiles;", "uint64_t* out_start = out_stop + n_tiles;", "out_stop[t] = f_stop;",
@@ -175,6 +185,10 @@ def test_layout_model_quotes_the_sources():
             text = " ".join(open(os.path.join(ROOT, "hip", name)).read().split())
             for line in lines:
                 assert " ".join(line.split()) in text, (name, line)
+    # the carving lines and the byte formula are stated in counted_output.hpp alone
+    for name in ("minimizer_abi.inc", "find_abi.inc", "orf_abi.inc", "minimizer_kernels.hpp", "find_kernels.hpp", "orf_kernels.hpp"):
+        text = open(os.path.join(ROOT, "hip", name)).read()
+        assert "& ~(uintptr_t)15" not in text and "& ~1ull" not in text and "return 16 +" not in text, name
 
 
 def test_guard_checker_on_synthetic_buffers():

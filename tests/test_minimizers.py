@@ -361,8 +361,8 @@ def test_minimizer_kernels_isa(product_asm):
     stores = [i for i in found["void cnt::minimizer_tiles<true>"]["body"] if "_store" in i and not i.startswith("ds_")]
     assert stores and all(i.startswith("global_store_dwordx2") and " nt" in i for i in stores), stores
     assert not [i for i in found["void cnt::minimizer_tiles<false>"]["body"] if i.startswith(("global_store_dwordx2", "buffer_store")) and " nt" in i]
-    m = re.search(r"^cnt::minimizer_scan\(.*?\): +; @(.*?)\.end_amdhsa_kernel", asm, re.S | re.M)
-    assert m, "minimizer_scan not in the product's assembly"
+    m = re.search(r"^cnt::counted_scan\(.*?\): +; @(.*?)\.end_amdhsa_kernel", asm, re.S | re.M)
+    assert m, "counted_scan not in the product's assembly"
     scan = m.group(1)
     assert "scratch_" not in scan and "s_xor_b64 exec, exec" not in scan
     assert re.search(r"\.amdhsa_private_segment_fixed_size\s+0\b", scan)
@@ -380,17 +380,27 @@ def minimizer_plan(n_len, k, w, launch_tiles=MIN_HW_LAUNCH_TILES):
     return tiles, (2 * -(-tiles // launch_tiles) + 1) if tiles else 0
 
 
+def assert_counted_output_source():
+    """what the three launchers reach through hip/counted_output.hpp: the one scan launch and the early exit for an empty input"""
+    src = open(os.path.join(ROOT, "hip", "counted_output.hpp")).read()
+    for line in ("hipLaunchKernelGGL(counted_scan, dim3(1), dim3(kCountedScanBlock), 0, s, w.counts, w.offs, n_tiles, static_cast<uint64_t*>(d_count));",
+                 "inline int counted_empty_dev(void* d_count, hipStream_t s) { return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK; }"):
+        assert line in src, line
+    assert src.count("hipLaunchKernelGGL(") == 1
+
+
 def test_minimizer_plan_matches_the_launcher_and_splitter_source():
     src = open(os.path.join(ROOT, "hip", "minimizer_kernels.hpp")).read()
     assert "constexpr int kMinBlock = 256;" in src and "constexpr uint32_t kMinTile = 2048, kMinMaxW = 256;" in src
     abi = open(os.path.join(ROOT, "hip", "minimizer_abi.inc")).read()
-    scan = "hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, count);"
-    for line in ("const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile, groups = (n_tiles + kMinGroup - 1) / kMinGroup;", scan,
-                 "if (n_win == 0) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;"):
+    scan = "counted_scan_enqueue(work, n_tiles, d_count, s);"
+    for line in ("const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile;", "const CountedScratch work = counted_carve(d_work, n_tiles);", scan,
+                 "if (n_win == 0) return counted_empty_dev(d_count, s);"):
         assert line in abi, line
+    assert_counted_output_source()
     # the two tile passes, each in launches of max_tiles_per_launch(kMinBlock) tiles, with the one scan launch between them
     tiles = "split_launches(n_tiles, kMinBlock, [&](uint64_t t, uint64_t n) {"
-    assert abi.count(tiles) == 2 and abi.count("minimizer_scan") == 1
+    assert abi.count(tiles) == 2 and abi.count("counted_scan") == 1
     assert abi.index(tiles) < abi.index(scan) < abi.rindex(tiles)
     assert_split_launches_by_max_tiles_per_launch()
     assert MIN_HW_LAUNCH_TILES == 8388544

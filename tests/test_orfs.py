@@ -18,6 +18,7 @@ import pytest
 from test_find_pattern import _set_codes, codes_of, words_of_codes
 from test_gpu_multi_launch import launch_tiles  # noqa: F401 -- the fixture: the lab build at 64 / 128 tiles per launch
 from test_kmers import assert_split_launches_by_max_tiles_per_launch
+from test_minimizers import assert_counted_output_source
 from test_translate import np_translate
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -453,8 +454,10 @@ def test_orf_kernels_isa():
         block = re.search(r"\.name:\s+cnt::%s\(.*?\.wavefront_size" % name, asm, re.S).group(0)
         assert re.search(r"\.uses_dynamic_stack:\s+false", block) and "dynamic_lds" not in block, name
     abi = open(os.path.join(ROOT, "hip", "orf_abi.inc")).read()
+    assert abi.count("counted_scan_enqueue(") == 1  # the scan's launch is the one in counted_output.hpp
+    abi += open(os.path.join(ROOT, "hip", "counted_output.hpp")).read()
     launches = re.findall(r"hipLaunchKernelGGL\((\w+), dim3\([^;]*?\), dim3\(\w+\), (\w+), s,", abi)
-    assert sorted(k for k, _ in launches) == sorted(ORF_KERNELS + ["minimizer_scan"]) and all(lds == "0" for _, lds in launches)
+    assert sorted(k for k, _ in launches) == sorted(ORF_KERNELS + ["counted_scan"]) and all(lds == "0" for _, lds in launches)
     assert len(isa_digest.kernels(asm)) < 60  # the product's templated kernels: none added
 
 
@@ -473,12 +476,16 @@ def test_orf_plan_matches_the_launcher_and_splitter_source():
     assert "constexpr int kOrfBlock = 256;" in src and "kOrfTileWords = kOrfBlock, kOrfTile = 32 * kOrfTileWords;" in src
     assert "constexpr int kOrfPairs = 6;" in src
     abi = open(os.path.join(ROOT, "hip", "orf_abi.inc")).read()
-    scan = "hipLaunchKernelGGL(minimizer_scan, dim3(1), dim3(kMinScanBlock), 0, s, counts, offs, n_tiles, static_cast<uint64_t*>(d_count));"
+    scan = "counted_scan_enqueue(work, n_tiles, d_count, s);"
     carry = "hipLaunchKernelGGL(orf_carry, dim3(both ? kOrfPairs : 3), dim3(kOrfCarryBlock), 0, s, sums, carry, n_tiles);"
     for line in ("uint64_t orf_tiles(size_t len) { return len < 3 ? 0 : (uint64_t)len / kOrfTile + 1; }", scan, carry,
-                 "if (len < 3) return d_count ? hip_rc(hipMemsetAsync(d_count, 0, 8, s)) : CNT_OK;",
-                 "return 16 + ((groups + 1) & ~1ull) * 8 + groups * kMinGroup * 4 + n_tiles * kOrfPairs * (4 + 2 * 8);"):
+                 "if (len < 3) return counted_empty_dev(d_count, s);", "const uint64_t n_tiles = orf_tiles(len);",
+                 "const CountedScratch work = counted_carve(d_work, n_tiles);",
+                 "uint64_t orf_work_bytes(uint64_t n_tiles) { return counted_scratch_bytes(n_tiles) + n_tiles * kOrfPairs * (4 + 2 * 8); }"):
         assert line in abi, line
+    assert_counted_output_source()
+    shared = open(os.path.join(ROOT, "hip", "counted_output.hpp")).read()
+    assert "return 16 + ((groups + 1) & ~1ull) * 8 + groups * kCountedGroup * 4;" in shared
     tiles = "split_launches(n_tiles, kOrfBlock, [&](uint64_t t, uint64_t n) { hipLaunchKernelGGL(orf_%s, dim3((unsigned)n), dim3(kOrfBlock), 0, s, a, t); });"
     at = [abi.index(tiles % k) for k in ("summary", "count", "write")]
     assert abi.count("split_launches(") == 3 and at[0] < abi.index(carry) < at[1] < abi.index(scan) < at[2]
