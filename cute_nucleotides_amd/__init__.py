@@ -12,7 +12,7 @@ from .n_to_bits import (bits_to_n_dev, bits_to_n_hip, bits_to_n_hip_into, bits_t
                         round_trip_checked_dev, round_trip_dev)
 from .n_to_bits2 import (bits_to_n2_dev, bits_to_n2_hip, bits_to_n2_hip_into, n_to_bits2_checked_dev, n_to_bits2_dev, n_to_bits2_hip,
                          n_to_bits2_hip_checked, n_to_bits2_hip_into)
-from .packed_ops import codon_set, orfs_dev, orfs_hip, orfs_work_bytes
+from .packed_ops import codon_set, hpc_dev, hpc_hip, hpc_minimizers_hip, hpc_work_bytes, orfs_dev, orfs_hip, orfs_work_bytes
 
 __all__ = [
     "n_to_bits_hip", "bits_to_n_hip", "n_to_bits_hip_sharded", "bits_to_n_hip_sharded",
@@ -21,4 +21,5 @@ __all__ = [
     "n_to_bits_hip_checked", "n_to_bits2_hip_checked", "n_to_bits_checked_dev", "n_to_bits2_checked_dev", "round_trip_checked_dev",
     "pinned_empty", "is_pinned", "host_registered",
     "orfs_hip", "orfs_dev", "orfs_work_bytes", "codon_set",
+    "hpc_hip", "hpc_dev", "hpc_work_bytes", "hpc_minimizers_hip",
 ]

@@ -135,6 +135,9 @@ SIGNATURES = {
     "cnt_orfs_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
     "cnt_orfs_dev": (_int, [_vp, _sz, _u64, _u64, _sz, _uint, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "cnt_orfs": (_int, [_vp, _sz, _u64, _u64, _sz, _uint, _vp, _vp, _vp, _sz, _vp]),
+    "cnt_hpc_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
+    "cnt_hpc_dev": (_int, [_vp, _sz, _uint, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_hpc": (_int, [_vp, _sz, _uint, _vp, _vp, _sz, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

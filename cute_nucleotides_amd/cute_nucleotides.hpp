@@ -303,6 +303,41 @@ inline Orfs orfs_hip(const uint64_t* bits, size_t words, size_t len, uint64_t st
     return r;
 }
 
+/// What packed::hpc_hip returns: the n run bases packed like any sequence in `out` (cnt_words_for(n) words), and pos[j] = where run
+/// j starts in the input; its length is pos[j + 1] - pos[j], and len - pos[n - 1] for the last.
+struct Hpc {
+    Vec<uint64_t> out;
+    size_t n = 0;
+    Vec<uint64_t> pos;
+};
+
+/// Homopolymer compression of the `len` nucleotides packed in `bits` (include/cute_nt.h "homopolymer compression"): every run of
+/// equal bases collapses to one base.  Every packed:: call takes (out.data(), out.size(), n); minimizers_hip on them and a look-up
+/// of its positions in `pos` are the input's homopolymer-compressed minimizers.  `with_pos` = false leaves `pos` empty.
+inline Hpc hpc_hip(const uint64_t* bits, size_t words, size_t len, bool with_pos = true) {
+    if (len > (words << 5)) detail::check(CNT_ELEN);
+    // random sequence: three runs per four bases; a longer result is fetched again at its reported size
+    const size_t guess = len / 4 * 3 + len / 64 + 64;
+    size_t cap = len < guess ? len : guess;
+    Hpc r;
+    uint64_t n = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        r.out.resize(cnt_words_for(cap));
+        if (with_pos) r.pos.resize(cap);
+        const int rc = cnt_hpc(bits, len, 0u, r.out.data(), with_pos ? r.pos.data() : nullptr, cap, &n);
+        if (rc == CNT_ECAP && attempt == 0) {
+            cap = n;
+            continue;
+        }
+        detail::check(rc);
+        break;
+    }
+    r.n = n;
+    r.out.resize(cnt_words_for(n));
+    if (with_pos) r.pos.resize(n);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -375,6 +410,20 @@ inline void orfs_hip_dev(const DeviceBuffer& bits, size_t len, uint64_t stops, u
     if (info && info->size_bytes() / 8 < cap) cap = info->size_bytes() / 8;
     detail::check(cnt_orfs_dev(bits.data(), len, stops, starts, min_len, both_strands ? CNT_ORF_BOTH_STRANDS : 0u, pos.data(), length.data(),
                                info ? info->data() : nullptr, cap, count.data(), work.data(), work.size_bytes(), nullptr));
+}
+inline size_t hpc_work_bytes(size_t len) {
+    size_t bytes = 0;
+    detail::check(cnt_hpc_work_bytes(len, &bytes));
+    return bytes;
+}
+/// Enqueue the homopolymer compression of `len` resident nucleotides (see packed::hpc_hip): `count` (one u64) is SET to the number
+/// of runs n, the first min(n, out_cap) run bases go to `out` packed and, when given, their positions to `pos`; `out` holds >=
+/// cnt_words_for(min(len, out_cap)) words, `pos` that many entries, `work` >= hpc_work_bytes(len) bytes of any contents.
+inline void hpc_hip_dev(const DeviceBuffer& bits, size_t len, DeviceBuffer& out, DeviceBuffer* pos, size_t out_cap, DeviceBuffer& count, DeviceBuffer& work) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    const size_t most = len < out_cap ? len : out_cap;
+    if (out.size_bytes() / 8 < cnt_words_for(most) || (pos && pos->size_bytes() / 8 < most)) throw std::out_of_range("hpc_hip_dev: an output is smaller than its footprint");
+    detail::check(cnt_hpc_dev(bits.data(), len, 0u, out.data(), pos ? pos->data() : nullptr, out_cap, count.data(), work.data(), work.size_bytes(), nullptr));
 }
 inline void sync() { detail::check(cnt_dev_sync(nullptr)); }
 inline void set_device(int device) { detail::check(cnt_set_device(device)); }  // what DeviceBuffer allocates on

@@ -2,7 +2,8 @@
 complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
 (w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
-frames, the open-reading-frame scan on one or both strands, and alphabet validation of ASCII buffers.  The reference does
+frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, and alphabet
+validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -363,6 +364,39 @@ def orfs_hip(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_A
     return _counted_hip(lib().cnt_orfs, cap, 3, info, _p(bits), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0)
 
 
+def hpc_hip(bits, length, with_pos=False):
+    """Homopolymer compression of the sequence (include/cute_nt.h "homopolymer compression"): every run of equal bases collapses
+    to one base.  Returns (out, n) -- np.uint64[words_for(n)] holding the n run bases packed like any sequence, so that every
+    call here takes (out, n) -- and with with_pos=True (out, n, pos): pos[j] is where run j starts in the input, its length
+    pos[j + 1] - pos[j] (length - pos[n - 1] for the last).  The output buffers start at a guess of n and are sized to the
+    reported n once if the guess was short."""
+    bits = _packed(bits, length)
+    cap = min(length, length // 4 * 3 + length // 64 + 64)  # a random sequence keeps three bases of four
+    for attempt in range(2):
+        out = np.empty(lib().cnt_words_for(cap), dtype=np.uint64)
+        pos = np.empty(cap, dtype=np.uint64) if with_pos else None
+        n = ctypes.c_uint64(0)
+        rc = lib().cnt_hpc(_p(bits), length, 0, _p(out), _p(pos) if with_pos else None, cap, ctypes.byref(n))
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            cap = n.value
+            continue
+        check(rc)
+        out = out[: lib().cnt_words_for(n.value)]
+        return (out, n.value, pos[: n.value]) if with_pos else (out, n.value)
+
+
+def hpc_minimizers_hip(bits, length, k, w, flags=0):
+    """The (w,k)-minimizers of the homopolymer-compressed sequence, in the coordinates of the sequence itself (minimap2 -H): hpc_hip
+    with positions, minimizers_hip on its (out, n), and each minimizer's position looked up in the run starts.  `flags` is 0 or
+    CNT_KMER_CANONICAL.  Returns numpy uint64 (pos, val): pos[j] is where the first run of minimizer j begins in `bits`, val[j] its
+    k-mer of run bases."""
+    if flags & ~CNT_KMER_CANONICAL:
+        raise ValueError("flags must be 0 or CNT_KMER_CANONICAL")
+    out, n, run_pos = hpc_hip(bits, length, with_pos=True)
+    pos, val = minimizers_hip(out, n, k, w, canonical=bool(flags & CNT_KMER_CANONICAL))
+    return run_pos[pos.astype(np.int64)], val
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -589,6 +623,43 @@ def orfs_dev(bits, length, stops=CNT_ORF_STOPS_STANDARD, starts=CNT_ORF_STARTS_A
     pos, (lens, inf), count, ptrs = _counted_dev(torch, bits, most, pos, [lens, _info_arg(info)], count, work, orfs_work_bytes(length))
     _enqueue(bits, lib().cnt_orfs_dev, ctypes.c_void_p(bits.data_ptr()), length, stops, starts, min_len, CNT_ORF_BOTH_STRANDS if both_strands else 0, *ptrs)
     return pos, lens, inf, count
+
+
+def hpc_work_bytes(length):
+    """bytes of device scratch cnt_hpc_dev needs for a sequence of this length (0 without a nucleotide)"""
+    return _work_bytes(lib().cnt_hpc_work_bytes, length)
+
+
+def hpc_dev(bits, length, out, count, work, pos=None, out_cap=None):
+    """Device tier of hpc_hip, enqueued on torch's current stream without a synchronisation; returns nothing.  All tensors are
+    the caller's, contiguous and on the input's device: `out` (int64) receives the run bases packed, `pos` (int64, optional) the
+    run starts, `count` (int64, one element) is SET to the number of runs n, `work` holds >= hpc_work_bytes(length) bytes of any
+    contents.  `out_cap` (runs; default: what `out`, and `pos` when given, can hold, at most length) bounds what is written: the
+    first min(n, out_cap) runs, inside words_for(min(length, out_cap)) words of `out`.  Every tensor may be reused across calls,
+    e.g. in a captured graph."""
+    torch = _packed_dev(bits, length)
+    for name, t, dtype in (("out", out, torch.int64), ("pos", pos, torch.int64), ("count", count, torch.int64), ("work", work, None)):
+        if t is None and name == "pos":
+            continue
+        if not hasattr(t, "is_cuda") or (dtype is not None and t.dtype != dtype):
+            raise TypeError("%s must be a%s tensor" % (name, "n int64" if dtype is not None else ""))
+        if not t.is_cuda or not t.is_contiguous() or t.device != bits.device:
+            raise ValueError("%s must be a contiguous CUDA tensor on the input's device" % name)
+    if count.numel() < 1:
+        raise ValueError("count must hold one element")
+    need = hpc_work_bytes(length)
+    if work.numel() * work.element_size() < need:
+        raise ValueError("work must hold >= %d bytes" % need)
+    fits = min(length, out.numel() * 32, pos.numel() if pos is not None else length)
+    if out_cap is None:
+        out_cap = fits
+    out_cap = int(out_cap)
+    if out_cap < 0 or min(length, out_cap) > fits:
+        raise ValueError("out_cap runs do not fit the outputs")
+    # an empty tensor has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    _enqueue(bits, lib().cnt_hpc_dev, ctypes.c_void_p(bits.data_ptr()), length, 0, ctypes.c_void_p(out.data_ptr() or count.data_ptr()),
+             ctypes.c_void_p(pos.data_ptr() or count.data_ptr()) if pos is not None else None, out_cap, ctypes.c_void_p(count.data_ptr()),
+             ctypes.c_void_p(work.data_ptr() or count.data_ptr()), work.numel() * work.element_size())
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -600,6 +600,52 @@ int cnt_orfs_dev(const void *d_bits, size_t len, uint64_t stops, uint64_t starts
 int cnt_orfs(const uint64_t *bits, size_t len, uint64_t stops, uint64_t starts, size_t min_len, unsigned flags, uint64_t *pos,
              uint64_t *length, uint64_t *info, size_t out_cap, uint64_t *count);
 
+/* Homopolymer compression: every run of equal bases of a packed sequence collapses to one base (minimap2's -H), and the result
+ * is a packed sequence again, so cnt_hpc -> cnt_minimizers -> pos[min_pos[j]] sketches a long read without leaving packed words.
+ * For the codes x_0 .. x_{len-1} (A=0, C=1, T=2, G=3, 32 per u64, LSB first):
+ *   kept       position i is kept iff i == 0 or x_i != x_{i-1}.  The kept positions in ascending order are p_0 < .. < p_{n-1};
+ *              n is the number of runs: n <= len, and n >= 1 when len >= 1.
+ *   out        the n codes x_{p_0}, x_{p_1}, .. packed exactly as the encoder packs them: every packed-domain call accepts
+ *              (out, n).  With m = min(n, out_cap) the words [0, cnt_words_for(m)) are written, and the code slots at or past
+ *              m in the last written word are 0.  out_cap is in nucleotides (runs), not in words.
+ *   footprint  of the call on out: cnt_words_for(min(len, out_cap)) words, the only bound known before the work.  The words of
+ *              the footprint behind the result have unspecified contents; nothing outside the footprint is ever written.
+ *   pos        optional (may be NULL): pos[j] = p_j as u64 for j < m; nothing at or past out_cap is written.
+ *   run length of run j: pos[j+1] - pos[j], and len - pos[n-1] for the last run.
+ *   Input bits beyond len are ignored: neither the zero padding nor garbage there extends or starts a run.
+ * The checks, in this order and all before any device work:
+ *   1. flags != 0 (none is defined): CNT_EINVAL, even without work; cnt_hpc_work_bytes: a NULL bytes
+ *   2. len == 0: CNT_OK with the count set to 0 (when a count pointer is given), nothing else is touched
+ *   3. a NULL or not 8-B aligned bits, out or count, a pos not 8-B aligned, the footprint of out or pos[0 .. min(len, out_cap))
+ *      overlapping the input words or each other (no in-place call: the input is read twice); d_work NULL or work_bytes below
+ *      the query's answer: CNT_EINVAL
+ * cnt_hpc_work_bytes: the device scratch cnt_hpc_dev needs; it depends on len only (0 when len == 0), about 5 B per 8192 nt.
+ * Device tier: enqueue-only (no allocation, no synchronisation, capturable in a graph), d_bits and d_out at any 8-B phase, len
+ *   up to 2^36, d_work any caller scratch that nobody needs zeroed.  *d_count (device u64) is SET to n whether or not the
+ *   result fitted: a caller whose buffers were too small reads n and calls again.
+ *   The output is a bit stream whose tile boundaries fall at any 2-bit phase of a word.  Tiles of 8192 positions, one word per
+ *   lane and the top code of the word in front of it.  Four passes: a count per tile (hpc_count), the minimizers' offset scan,
+ *   one lane per tile that zeroes the at most two output words the tile shares with others (hpc_zero_edges), and the write
+ *   pass (hpc_write, hpc_write_pos), which skips the tiles inside a run, compresses each lane's word to its kept codes in five
+ *   log steps, assembles the tile's output words in LDS and stores them in one coalesced pass -- the shared words by a 64-bit
+ *   atomic compare-and-swap (the one merge a pinned buffer behind a PCIe link supports), the others plainly; positions are
+ *   staged in LDS too, so that a wave stores them contiguously.
+ *   Measured on one MI355X, 2026-10-19, product build (DESIGN.md 4 "homopolymer compression", profiles/hpc_bench.jsonl): 2^30 nt
+ *   of random ACGT (n = 0.75 len) take 0.427 ms without pos and 1.922 ms with it; 2^30 nt of {A,C} with a C at one position in
+ *   64 (n = len / 32.5) take 0.373 / 0.432 ms; cnt_complement_dev on the same words takes 0.091 ms in the same run, so the
+ *   call costs 4.7x / 21.2x and 4.1x / 4.8x the complement.  rocprofv3 --kernel-trace --stats of three calls of each kind
+ *   (profiles/hpc_kernel_trace.md) splits a call into hpc_count 92 us, counted_scan 20 us, hpc_zero_edges 6 us and the write
+ *   pass: hpc_write 321 us (random ACGT) / 273 us (long runs), hpc_write_pos 1760 / 343 us.  The write pass is the longest.
+ *   With pos on random ACGT it stores 6.4 GB of positions at 3.7 TB/s; without pos it moves 0.47 GB in 0.32 ms, 3.5x the time
+ *   hpc_count takes for the same read, so it is not bound by memory there.  What bounds it was not isolated: no counters were
+ *   collected.
+ * Host tier: synchronous; pinned bits, out and pos are used in place.  *count = n always; when n > out_cap the first out_cap
+ *   codes and positions are written and the call returns CNT_ECAP. */
+int cnt_hpc_work_bytes(size_t len, size_t *bytes);
+int cnt_hpc_dev(const void *d_bits, size_t len, unsigned flags, void *d_out, void *d_pos, size_t out_cap, void *d_count,
+                void *d_work, size_t work_bytes, void *stream);
+int cnt_hpc(const uint64_t *bits, size_t len, unsigned flags, uint64_t *out, uint64_t *pos, size_t out_cap, uint64_t *count);
+
 /* (w,k)-minimizers, 1 <= k <= 32, 1 <= w <= 256, flags 0 or CNT_KMER_CANONICAL.  With m = len-k+1 k-mers:
  *   x_i   = the value cnt_kmers writes for k-mer i with the same flags (forward or canonical), i < m
  *   h_i   = fmix64(x_i), the splitmix64 finaliser mod 2^64: z = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9,

@@ -83,6 +83,9 @@ extern "C" {
     fn cnt_orfs_work_bytes(len: usize, bytes: *mut usize) -> c_int;
     fn cnt_orfs_dev(d_bits: *const c_void, len: usize, stops: u64, starts: u64, min_len: usize, flags: c_uint, d_pos: *mut c_void, d_length: *mut c_void, d_info: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_orfs(bits: *const u64, len: usize, stops: u64, starts: u64, min_len: usize, flags: c_uint, pos: *mut u64, length: *mut u64, info: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
+    fn cnt_hpc_work_bytes(len: usize, bytes: *mut usize) -> c_int;
+    fn cnt_hpc_dev(d_bits: *const c_void, len: usize, flags: c_uint, d_out: *mut c_void, d_pos: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_hpc(bits: *const u64, len: usize, flags: c_uint, out: *mut u64, pos: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -713,6 +716,32 @@ pub fn orfs_hip(bits: &[u64], len: usize, stops: u64, starts: u64, min_len: usiz
     (pos, length, info)
 }
 
+/// Homopolymer compression as `(out, n, pos)`: every run of equal bases collapses to one base.  `out` holds the `n` run bases
+/// packed like any sequence (every packed-domain call takes `(&out, n)`), and `pos[j]` is where run `j` starts in the input, so
+/// its length is `pos[j + 1] - pos[j]` (`len - pos[n - 1]` for the last).  `minimizers_hip(&out, n, ..)` and a look-up of its
+/// positions in `pos` give the input's homopolymer-compressed minimizers.
+pub fn hpc_hip(bits: &[u64], len: usize) -> (Vec<u64>, usize, Vec<u64>) {
+    need(bits, len);
+    // random sequence: three runs per four bases; a longer result is fetched again at its reported size
+    let mut cap = std::cmp::min(len, len / 4 * 3 + len / 64 + 64);
+    let mut out: Vec<u64> = vec![0u64; words_for(cap)];
+    let mut pos: Vec<u64> = Vec::with_capacity(cap);
+    let mut n: u64 = 0;
+    unsafe {
+        let fits = cnt_hpc(bits.as_ptr(), len, 0, out.as_mut_ptr(), pos.as_mut_ptr(), cap, &mut n) == 0;
+        if !fits {
+            // CNT_ECAP left the count in n; any other status comes back from the second call and panics in check
+            cap = n as usize;
+            out = vec![0u64; words_for(cap)];
+            pos = Vec::with_capacity(cap);
+            check(cnt_hpc(bits.as_ptr(), len, 0, out.as_mut_ptr(), pos.as_mut_ptr(), cap, &mut n));
+        }
+        pos.set_len(n as usize);
+    }
+    out.truncate(words_for(n as usize));
+    (out, n as usize, pos)
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -949,6 +978,32 @@ pub fn orfs_hip_dev(d_bits: &DeviceBuffer, len: usize, stops: u64, starts: u64, 
         None => std::ptr::null_mut(),
     };
     unsafe { check(cnt_orfs_dev(d_bits.ptr, len, stops, starts, min_len, flags, d_pos.ptr, d_length.ptr, info_ptr, cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `hpc_hip_dev` needs for a sequence of `len` nucleotides (0 when there is none).
+pub fn hpc_work_bytes(len: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_hpc_work_bytes(len, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the homopolymer compression of `len` device-resident nucleotides (see `hpc_hip`): `d_count` (one u64) is SET to the
+/// number of runs n, the first min(n, out_cap) run bases go to `d_out` packed and, when given, their positions to `d_pos`;
+/// `d_out` holds at least `words_for(min(len, out_cap))` words, `d_pos` that many entries, `d_work` at least `hpc_work_bytes`
+/// bytes of any contents.
+pub fn hpc_hip_dev(d_bits: &DeviceBuffer, len: usize, d_out: &DeviceBuffer, d_pos: Option<&DeviceBuffer>, out_cap: usize, d_count: &DeviceBuffer, d_work: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    let most = std::cmp::min(len, out_cap);
+    if d_out.bytes / 8 < words_for(most) || d_pos.map_or(false, |v| v.bytes / 8 < most) {
+        panic!("an output is smaller than its footprint");
+    }
+    let pos_ptr = match d_pos {
+        Some(v) => v.ptr,
+        None => std::ptr::null_mut(),
+    };
+    unsafe { check(cnt_hpc_dev(d_bits.ptr, len, 0, d_out.ptr, pos_ptr, out_cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
