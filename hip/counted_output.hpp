@@ -5,7 +5,7 @@
 //   2. counted_scan: one workgroup sums the counts by groups of kCountedGroup tiles (one 64-B read per lane), writes each
 //      group's exclusive offset to offs[group] and SETS *count to the total;
 //   3. a write pass of its own: the same tiles again, recomputed, store their entries at counted_tile_base() + their rank in the
-//      tile, below out_cap only.
+//      tile (word_tile.hpp: tile_rank_post, tile_total, tile_before), below out_cap only.
 // A first scan of one u64 per tile, read and written by one lane per 16 consecutive tiles, took 0.52 ms of an 8.2-ms minimizer
 // call at 2^30 nt: its loads and stores were 64 cache lines per wave instruction.
 //
@@ -26,6 +26,7 @@
 #include <initializer_list>
 
 #include "util_kernels.hpp"
+#include "word_tile.hpp"
 
 namespace cnt {
 
@@ -38,17 +39,6 @@ __device__ __forceinline__ uint64_t counted_tile_base(const uint64_t* offs, cons
 #pragma unroll
     for (int q = 0; q < kCountedGroup - 1; ++q) b += (uint64_t)q < tile % kCountedGroup ? g[q] : 0u;
     return b;
-}
-
-// the inclusive sum of c over the lanes 0 .. lane of a wave (lane order = output order)
-__device__ __forceinline__ uint32_t wave_inclusive_sum(uint32_t c, uint32_t lane) {
-    uint32_t x = c;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= (uint32_t)o) x += y;
-    }
-    return x;
 }
 
 // One workgroup; lane j of a pass sums the kCountedGroup counts of group j (four 16-B loads: counts is 16-B aligned and holds
@@ -74,8 +64,8 @@ __global__ __launch_bounds__(kCountedScanBlock) void counted_scan(const uint32_t
         uint64_t x = sum;  // inclusive scan over the wave
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t lo = __shfl_up((uint32_t)x, o, 64), hi = __shfl_up((uint32_t)(x >> 32), o, 64);
-            if (lane >= (uint32_t)o) x += ((uint64_t)hi << 32) | lo;
+            const uint64_t y = shfl_up_u64(x, o);
+            if (lane >= (uint32_t)o) x += y;
         }
         if (lane == 63) s_w[wave] = x;
         __syncthreads();

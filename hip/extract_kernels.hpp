@@ -4,8 +4,7 @@
 //
 // Output word j of a record is ONE 64-bit window of the input at an arbitrary bit phase: forward the window at nucleotide
 // start + 32j, reversed the window at start + region_len - 32 - 32j with its codes reversed and complemented (reverse_codes64,
-// ^ 0xAAAA...: packed_ops_kernels.hpp).  A window straddles two input words; the funnel is the branch-free
-// (x << 1) << (63 - sh) of reverse_complement_tiles.  Two shapes:
+// ^ 0xAAAA...).  A window straddles two input words; the funnel is the branch-free funnel64 (both: word_tile.hpp).  Two shapes:
 //   extract_words       one thread per output word, words [j0, j0 + w) of every record: short windows (a gather: address
 //                       arithmetic and two dependent loads per word), the remainder of long records behind their tiles, and the
 //                       words cnt_subseq_dev peels in front of the first 128-B line of its output.
@@ -120,11 +119,13 @@ __device__ __forceinline__ void extract_tile(const ExtractArgs& a, uint64_t j_ba
         const uint32_t sh = 2u * ((uint32_t)S & 31u);
         const uint64_t avail = r.rejected ? 0 : a.words - J;  // J < words for an accepted region
         const __amdgpu_buffer_rsrc_t rin = rsrc_of(a.in + J * 8, (uint32_t)(avail < kExtractTileWords + 2 ? avail : kExtractTileWords + 2) * 8);
-        const u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, l * 16, 0, kNT));
+        const vu4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, l * 16, 0, kNT);
         const vu2 e = __builtin_amdgcn_raw_buffer_load_b64(rin, sh ? l * 16 + 16 : kExtractOutside, 0, kNT);
-        const uint64_t w0 = ((uint64_t)v.y << 32) | v.x, w1 = ((uint64_t)v.w << 32) | v.z, w2 = ((uint64_t)e[1] << 32) | e[0];
-        win0 = (w0 >> sh) | ((w1 << 1) << (63 - sh));
-        win1 = (w1 >> sh) | ((w2 << 1) << (63 - sh));
+        uint64_t w0, w1;
+        u64_pair(v, w0, w1);
+        const uint64_t w2 = ((uint64_t)e[1] << 32) | e[0];
+        win0 = funnel64(w0, w1, sh);
+        win1 = funnel64(w1, w2, sh);
     } else {
         const int64_t P = (int64_t)(r.start + a.region_len) - 32 - (int64_t)(j << 5);
         const int64_t lo = r.rejected ? 0 : (P >> 5) - (int64_t)(kExtractTileWords - 1);  // the tile's lowest window word: >= -1
@@ -135,17 +136,18 @@ __device__ __forceinline__ void extract_tile(const ExtractArgs& a, uint64_t j_ba
         const __amdgpu_buffer_rsrc_t rin = rsrc_of(a.in + b * 8, (uint32_t)(avail < kExtractTileWords + 2 ? avail : kExtractTileWords + 2) * 8);
         const uint32_t off_e = neg ? (l == kExtractBlock - 1 ? kExtractOutside : (kExtractTileWords - 3 - 2 * l) * 8)
                                    : (sh ? (kExtractTileWords - 2 * l) * 8 : kExtractOutside);
-        const u32x4 v = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (kExtractTileWords - 2 - 2 * l) * 8, 0, kNT));
+        const vu4 v = __builtin_amdgcn_raw_buffer_load_b128(rin, (kExtractTileWords - 2 - 2 * l) * 8, 0, kNT);
         const vu2 e = __builtin_amdgcn_raw_buffer_load_b64(rin, off_e, 0, kNT);
-        const uint64_t x0 = ((uint64_t)v.y << 32) | v.x, x1 = ((uint64_t)v.w << 32) | v.z, y = ((uint64_t)e[1] << 32) | e[0];
+        uint64_t x0, x1;
+        u64_pair(v, x0, x1);
+        const uint64_t y = ((uint64_t)e[1] << 32) | e[0];
         const uint64_t wm = neg ? y : x0, wj = neg ? x0 : x1, wp = neg ? x1 : y;  // input words J-2l-1, J-2l, J-2l+1
-        win0 = reverse_codes64((wj >> sh) | ((wp << 1) << (63 - sh))) ^ 0xAAAAAAAAAAAAAAAAull;
-        win1 = reverse_codes64((wm >> sh) | ((wj << 1) << (63 - sh))) ^ 0xAAAAAAAAAAAAAAAAull;
+        win0 = reverse_codes64(funnel64(wj, wp, sh)) ^ 0xAAAAAAAAAAAAAAAAull;
+        win1 = reverse_codes64(funnel64(wm, wj, sh)) ^ 0xAAAAAAAAAAAAAAAAull;
     }
     const uint64_t live = r.rejected ? 0 : ~0ull;  // a rejected region's tiles store zeros
     const uint64_t o0 = win0 & extract_keep(a.region_len, j + 2 * l) & live, o1 = win1 & extract_keep(a.region_len, j + 2 * l + 1) & live;
-    const u32x4 o = {(uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32)};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vu4, o), rout, l * 16, 0, kSC0 | kSC1 | kNT);
+    __builtin_amdgcn_raw_buffer_store_b128(pack_u64x2(o0, o1), rout, l * 16, 0, kSC0 | kSC1 | kNT);
     if (r.rejected && j == 0 && l == 0 && a.rejected)  // the region's word 0 is in this tile: counted here, once
         (void)__hip_atomic_fetch_add(a.rejected, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }

@@ -14,9 +14,9 @@
 //   3. find_write_*: a tile whose count is 0 returns at once (nearly every tile of a real search); the others are
 //      recomputed (0.25 B/nt: cheaper than staging candidates), a workgroup prefix sum over the lanes' hit counts places each
 //      lane's run, and the lane stores its hits in window order, forward before reverse, below out_cap only.
-// Shape of a tile, as in kmer_count_kernels.hpp: lane j owns the 32 windows that START in word j of the tile; it reads that word
-// and the next (one 16-B raw-buffer load at 8-B grain, `nt`) and walks the 32 windows with constant funnel shifts into two hit
-// masks (bit r: window r hits), one per strand.  Pattern, care masks and the bound are kernel arguments: wave-uniform, in SGPRs.
+// Shape of a tile, as in word_tile.hpp: lane j owns the 32 windows that START in word j of the tile; it reads that word and the
+// next (word_tile_pair) and walks the 32 windows with constant funnel shifts into two hit masks (bit r: window r hits), one per
+// strand.  Pattern, care masks and the bound are kernel arguments: wave-uniform, in SGPRs.
 // WIDE = false (k <= 16): a window and everything compared with it is one dword -- half the VALU work of the 64-bit form.
 #pragma once
 
@@ -57,8 +57,7 @@ __device__ __forceinline__ uint32_t find_dist(uint64_t x, uint64_t p, uint64_t c
 // window r (0..31) of the 32 that start in word `lo`, `hi` the word behind it; WIDE = false keeps its low 16 codes
 template <bool WIDE>
 __device__ __forceinline__ uint64_t find_window(uint64_t lo, uint64_t hi, uint32_t r) {
-    // branch-free funnel: (hi << 1) << (63 - sh) is hi << (64 - sh) for sh = 2..62 and 0 for sh = 0
-    const uint64_t win = (lo >> (2 * r)) | ((hi << 1) << (63 - 2 * r));
+    const uint64_t win = funnel64(lo, hi, 2 * r);
     return WIDE ? win : (uint64_t)(uint32_t)win;
 }
 
@@ -72,10 +71,7 @@ __device__ __forceinline__ void find_lane_masks(uint64_t lo, uint64_t hi, const 
     rm = 0;
 #pragma unroll
     for (uint32_t r = 0; r < 32; ++r) {
-        const uint32_t d = r >> 4, sh = 2 * (r & 15u);
-        const uint32_t w0 = sh ? __builtin_amdgcn_alignbit(a[d + 1], a[d], sh) : a[d];
-        const uint32_t w1 = !WIDE ? 0u : sh ? __builtin_amdgcn_alignbit(a[d + 2], a[d + 1], sh) : a[d + 1];
-        const uint64_t win = ((uint64_t)w1 << 32) | w0;
+        const uint64_t win = ((uint64_t)(WIDE ? window_dword(a + 1, r) : 0u) << 32) | window_dword(a, r);
         fm |= (find_dist<WIDE>(win, p.fwd, p.fwd_care) <= p.max_mismatches ? 1u : 0u) << r;
         if constexpr (BOTH) rm |= (find_dist<WIDE>(win, p.rev, p.rev_care) <= p.max_mismatches ? 1u : 0u) << r;
     }
@@ -93,46 +89,28 @@ __device__ __forceinline__ void find_tile(const uint8_t* __restrict__ in, uint64
     __shared__ uint32_t s_cnt[kFindWaves];
     __shared__ uint64_t s_base;
     const uint64_t tile = first_tile + blockIdx.x, w0 = tile * kFindTileWords;
-    const uint32_t j = threadIdx.x, lane = j & 63u, wave = j >> 6;
+    const uint32_t j = threadIdx.x;
     if constexpr (WRITE) {
         if (counts[tile] == 0) return;
     }
     uint64_t lo, hi;
-    if (w0 + kFindTileWords + 1 <= words) {
-        const __amdgpu_buffer_rsrc_t rin = rsrc_of(in + w0 * 8, (uint32_t)(kFindTileWords + 1) * 8);
-        const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, j * 8, 0, kNT));
-        lo = ((uint64_t)q.y << 32) | q.x;
-        hi = ((uint64_t)q.w << 32) | q.z;
-    } else {
-        const uint64_t* in64 = reinterpret_cast<const uint64_t*>(in);
-        const uint64_t w = w0 + j;
-        lo = w < words ? in64[w] : 0;
-        hi = w + 1 < words ? in64[w + 1] : 0;
-    }
+    word_tile_pair<kFindTileWords>(in, words, w0, j, lo, hi);
     const uint64_t i0 = (w0 + j) * 32;
-    const uint32_t valid = i0 >= m ? 0u : (m - i0 >= 32 ? ~0u : (1u << (uint32_t)(m - i0)) - 1u);
+    const uint32_t valid = codes_below(i0, m);
     uint32_t fm, rm;
     find_lane_masks<WIDE, BOTH>(lo, hi, p, fm, rm);
     fm &= valid;
     rm &= valid;
     const uint32_t c = (uint32_t)__popc(fm) + (uint32_t)__popc(rm);
-    const uint32_t x = wave_inclusive_sum(c, lane);  // lane order = window order
-    if (lane == 63) s_cnt[wave] = x;
+    const uint32_t x = tile_rank_post(c, s_cnt);  // lane order = window order
     if constexpr (WRITE) {
         if (j == 0) s_base = counted_tile_base(offs, counts, tile);
     }
     __syncthreads();
     if constexpr (!WRITE) {
-        if (j == 0) {
-            uint32_t total = 0;
-#pragma unroll
-            for (int q = 0; q < kFindWaves; ++q) total += s_cnt[q];
-            counts[tile] = total;
-        }
+        if (j == 0) counts[tile] = tile_total<kFindWaves>(s_cnt);
     } else {
-        uint64_t at = s_base + (x - c);
-#pragma unroll
-        for (int q = 0; q < kFindWaves - 1; ++q) at += q < (int)wave ? s_cnt[q] : 0u;
+        uint64_t at = s_base + tile_before<kFindWaves>(s_cnt, x - c);
         // the lane's hits in window order, forward before reverse; the distance is recomputed for the few windows that hit
         for (uint32_t any = fm | rm; any; any &= any - 1) {
             const uint32_t r = (uint32_t)__builtin_ctz(any);

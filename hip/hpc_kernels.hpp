@@ -19,8 +19,8 @@
 //                      (hpc_merge), every other word is stored plainly.  The positions go through LDS as u16 offsets into the
 //                      tile, so that a wave's stores are contiguous.
 // Codes at or past out_cap are clipped before the LDS stage; no word at or past cnt_words_for(min(n, out_cap)) is touched.
-// Shape of a tile, as in find_kernels.hpp: lane j owns the 32 positions of word j of the tile; it reads that word and the one in
-// FRONT of it (one 16-B raw-buffer load at 8-B grain, `nt`), whose top code decides position 0 of the lane.
+// Shape of a tile, as in word_tile.hpp: lane j owns the 32 positions of word j of the tile; it reads that word and the one in
+// FRONT of it (word_tile_pair with BACK = 1), whose top code decides position 0 of the lane.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -51,17 +51,7 @@ __device__ __forceinline__ uint64_t hpc_keep(const HpcArgs& a, uint64_t tile, ui
     const uint32_t j = threadIdx.x;
     const uint64_t w0 = tile * kHpcTileWords;
     uint64_t prev;
-    if (tile > 0 && w0 + kHpcTileWords <= a.words) {
-        const __amdgpu_buffer_rsrc_t rin = rsrc_of(a.in + (w0 - 1) * 8, (uint32_t)(kHpcTileWords + 1) * 8);
-        const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, j * 8, 0, kNT));
-        prev = ((uint64_t)q.y << 32) | q.x;
-        w = ((uint64_t)q.w << 32) | q.z;
-    } else {
-        const uint64_t* in64 = reinterpret_cast<const uint64_t*>(a.in);
-        const uint64_t i = w0 + j;
-        w = i < a.words ? in64[i] : 0;
-        prev = i > 0 && i - 1 < a.words ? in64[i - 1] : 0;
-    }
+    word_tile_pair<kHpcTileWords, 1>(a.in, a.words, w0, j, prev, w);  // tile 0 reads guarded: word -1 is 0
     const uint64_t i0 = (w0 + j) * 32;
     const uint64_t d = w ^ ((w << 2) | (prev >> 62));  // code r against code r - 1
     uint64_t keep = (d | (d >> 1)) & 0x5555555555555555ull;
@@ -123,18 +113,11 @@ __device__ __forceinline__ void hpc_merge(uint64_t* p, unsigned long long v) {
 __global__ __launch_bounds__(kHpcBlock) void hpc_count(HpcArgs a, uint64_t first_tile) {
     __shared__ uint32_t s_cnt[kHpcWaves];
     const uint64_t tile = first_tile + blockIdx.x;
-    const uint32_t j = threadIdx.x, lane = j & 63u, wave = j >> 6;
     uint64_t w;
     const uint64_t keep = hpc_keep(a, tile, w);
-    const uint32_t x = wave_inclusive_sum((uint32_t)__popcll(keep), lane);
-    if (lane == 63) s_cnt[wave] = x;
+    tile_rank_post((uint32_t)__popcll(keep), s_cnt);
     __syncthreads();
-    if (j == 0) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int q = 0; q < kHpcWaves; ++q) total += s_cnt[q];
-        a.counts[tile] = total;
-    }
+    if (threadIdx.x == 0) a.counts[tile] = tile_total<kHpcWaves>(s_cnt);
 }
 
 // pass 3: lane = tile first_block * kHpcBlock + blockIdx.x * kHpcBlock + threadIdx.x
@@ -156,7 +139,7 @@ __device__ __forceinline__ void hpc_write_tile(const HpcArgs& a, uint64_t first_
     __shared__ uint32_t s_cnt[kHpcWaves];
     __shared__ HpcSpan s_span;
     const uint64_t tile = first_tile + blockIdx.x;
-    const uint32_t j = threadIdx.x, lane = j & 63u, wave = j >> 6;
+    const uint32_t j = threadIdx.x;
     uint64_t w;
     const uint64_t keep = hpc_keep(a, tile, w);  // the load is under way before the count is waited for
     const uint32_t total = a.counts[tile];
@@ -167,14 +150,11 @@ __device__ __forceinline__ void hpc_write_tile(const HpcArgs& a, uint64_t first_
         s_span = hpc_span(a, tile, total);
     }
     const uint32_t c = (uint32_t)__popcll(keep);
-    const uint32_t x = wave_inclusive_sum(c, lane);  // lane order = position order
-    if (lane == 63) s_cnt[wave] = x;
+    const uint32_t x = tile_rank_post(c, s_cnt);  // lane order = position order
     __syncthreads();
     const HpcSpan s = s_span;
     if (s.room == 0) return;  // everything of the tile lies at or past out_cap
-    uint32_t before = x - c;  // the tile's kept positions in front of the lane
-#pragma unroll
-    for (int q = 0; q < kHpcWaves - 1; ++q) before += q < (int)wave ? s_cnt[q] : 0u;
+    const uint32_t before = tile_before<kHpcWaves>(s_cnt, x - c);  // the tile's kept positions in front of the lane
     const uint32_t phase = (uint32_t)(s.base & 31u);
     const uint32_t cc = before >= s.room ? 0u : (s.room - before < c ? s.room - before : c);  // the lane's codes below out_cap
     uint64_t frag = hpc_compress(w, keep);

@@ -8,8 +8,8 @@
 //                      flushed once at the end into the caller's u64 table with 64-bit global atomics;
 //   kmer_count<false>  larger k: 64-bit global atomics straight into the caller's table.
 // Shape of both: persistent workgroups of 1024 lanes stride over tiles of 1024 input words.  Lane j of a tile owns the 32
-// k-mers that START in word j of the tile: it reads that word and the next (one 16-B raw-buffer load at 8-B grain, `nt`, as
-// kmer_tiles does) and walks the 32 windows with constant funnel shifts.  k <= 12 means 2k <= 24 bits, so a window is the
+// k-mers that START in word j of the tile: it reads that word and the next (word_tile.hpp: word_tile_pair) and walks the 32
+// windows with constant funnel shifts.  k <= 12 means 2k <= 24 bits, so a window is the
 // low dword of the 64-bit funnel and the canonical form is a 32-bit bit reverse.
 //
 // The two hazards of a histogram:
@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
+#include "word_tile.hpp"
 
 namespace cnt {
 
@@ -53,9 +54,7 @@ __host__ __device__ constexpr uint32_t kmer_count_replica_log2(uint32_t k) {
 template <bool CANONICAL>
 __device__ __forceinline__ uint32_t kmer_count_finish(uint32_t fwd, uint32_t k) {
     if constexpr (CANONICAL) {
-        uint32_t x = __builtin_bitreverse32(fwd ^ 0xAAAAAAAAu);
-        x = ((x >> 1) & 0x55555555u) | ((x & 0x55555555u) << 1);
-        const uint32_t rc = x >> (32 - 2 * k);
+        const uint32_t rc = reverse_codes32(fwd ^ 0xAAAAAAAAu) >> (32 - 2 * k);
         return rc < fwd ? rc : fwd;
     } else {
         return fwd;
@@ -104,20 +103,7 @@ __global__ __launch_bounds__(kKmerCountBlock) void kmer_count(const uint8_t* __r
         for (uint32_t i = j; i < kKmerCountSlots; i += kKmerCountBlock) table[i] = 0;
         __syncthreads();
     }
-    auto load = [&](uint64_t t, uint64_t& lo, uint64_t& hi) {
-        const uint64_t w0 = t * kKmerCountTileWords;
-        if (w0 + kKmerCountTileWords + 1 <= words) {
-            const __amdgpu_buffer_rsrc_t rin = rsrc_of(in + w0 * 8, (uint32_t)(kKmerCountTileWords + 1) * 8);
-            const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, j * 8, 0, kNT));
-            lo = ((uint64_t)q.y << 32) | q.x;
-            hi = ((uint64_t)q.w << 32) | q.z;
-        } else {
-            const uint64_t* in64 = reinterpret_cast<const uint64_t*>(in);
-            const uint64_t w = w0 + j;
-            lo = w < words ? in64[w] : 0;
-            hi = w + 1 < words ? in64[w + 1] : 0;
-        }
-    };
+    auto load = [&](uint64_t t, uint64_t& lo, uint64_t& hi) { word_tile_pair<kKmerCountTileWords>(in, words, t * kKmerCountTileWords, j, lo, hi); };
     uint64_t t = blockIdx.x, lo = 0, hi = 0;
     if (t < n_tiles) load(t, lo, hi);
     while (t < n_tiles) {

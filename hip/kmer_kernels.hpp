@@ -13,24 +13,19 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
+#include "word_tile.hpp"
 
 namespace cnt {
 
 constexpr int kKmerBlock = 256, kKmerU = 2;  // U: k-mer pairs per lane (profiles/kmers_tile_ab.jsonl)
 constexpr uint64_t kKmersPerTile = (uint64_t)kKmerBlock * 2 * kKmerU;
 
-// reverse the order of the 32 two-bit codes of a word (bit reverse, then swap the two bits back inside each code)
-__device__ __forceinline__ uint64_t kmer_reverse_codes(uint64_t x) {
-    x = __builtin_bitreverse64(x);
-    return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);
-}
-
 // `fwd` holds k codes in its low 2k bits, zero above.  Complementing sets the unused high codes to 2; reversing moves them
 // to the low end, where the shift by 64-2k drops them.
 template <bool CANONICAL>
 __device__ __forceinline__ uint64_t kmer_finish(uint64_t fwd, uint32_t k) {
     if constexpr (CANONICAL) {
-        const uint64_t rc = kmer_reverse_codes(fwd ^ 0xAAAAAAAAAAAAAAAAull) >> (64 - 2 * k);
+        const uint64_t rc = reverse_codes64(fwd ^ 0xAAAAAAAAAAAAAAAAull) >> (64 - 2 * k);
         return rc < fwd ? rc : fwd;
     } else {
         return fwd;
@@ -49,21 +44,19 @@ __global__ __launch_bounds__(BLOCK) void kmer_tiles(const uint8_t* __restrict__ 
     const __amdgpu_buffer_rsrc_t rin = rsrc_of(in + wa * 8, (BLOCK * U / 16 + 2) * 8);
     const __amdgpu_buffer_rsrc_t rout = rsrc_of(out + a * 8, BLOCK * 16 * U);
     const uint32_t j = threadIdx.x, a31 = (uint32_t)a & 31u;
-    u32x4 q[U];
+    vu4 q[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u)
-        q[u] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, ((a31 + 2 * (u * BLOCK + j)) >> 5) * 8, 0, kNT));
+    for (int u = 0; u < U; ++u) q[u] = __builtin_amdgcn_raw_buffer_load_b128(rin, ((a31 + 2 * (u * BLOCK + j)) >> 5) * 8, 0, kNT);
     const uint64_t mask = ~0ull >> (64 - 2 * k);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-        const uint64_t lo = ((uint64_t)q[u].y << 32) | q[u].x, hi = ((uint64_t)q[u].w << 32) | q[u].z;
+        uint64_t lo, hi;
+        u64_pair(q[u], lo, hi);
         const uint32_t sh = 2u * ((a31 + 2 * (u * BLOCK + j)) & 31u);
-        // branch-free funnel: (hi << 1) << (63 - sh) is hi << (64 - sh) for sh = 2..62 and 0 for sh = 0
-        const uint64_t win0 = (lo >> sh) | ((hi << 1) << (63 - sh));
+        const uint64_t win0 = funnel64(lo, hi, sh);
         const uint64_t win1 = (win0 >> 2) | (((hi >> sh) & 3ull) << 62);
         const uint64_t o0 = kmer_finish<CANONICAL>(win0 & mask, k), o1 = kmer_finish<CANONICAL>(win1 & mask, k);
-        const u32x4 o = {(uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32)};
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vu4, o), rout, (u * BLOCK + j) * 16, 0, kSC0 | kSC1 | kNT);
+        __builtin_amdgcn_raw_buffer_store_b128(pack_u64x2(o0, o1), rout, (u * BLOCK + j) * 16, 0, kSC0 | kSC1 | kNT);
     }
 }
 

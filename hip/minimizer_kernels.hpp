@@ -30,14 +30,14 @@ constexpr int kMinWinRounds = (int)(kMinTile / kMinBlock);             // window
 constexpr int kMinWaves = kMinBlock / 64;
 static_assert(kMinEntries % kMinBlock == 0 && kMinTile % kMinBlock == 0 && kMinEntries < 65536, "local indices are u16");
 
-// k-mer i (i + k <= len) as cnt_kmers writes it: the funnel of kmer_tiles over words i>>5 and i>>5 + 1.  The second word is
+// k-mer i (i + k <= len) as cnt_kmers writes it: funnel64 (word_tile.hpp) over words i>>5 and i>>5 + 1.  The second word is
 // clamped to the last one: when it does not exist the k-mer lies inside word i>>5, and the mask drops what the clamp brought.
 __device__ __forceinline__ uint64_t minimizer_kmer(const uint64_t* __restrict__ in, uint64_t last_word, uint64_t i, uint32_t k,
                                                    bool canonical) {
     const uint64_t wd = i >> 5;
     const uint32_t sh = 2u * ((uint32_t)i & 31u);
     const uint64_t lo = in[wd], hi = in[wd + 1 <= last_word ? wd + 1 : last_word];
-    const uint64_t x = ((lo >> sh) | ((hi << 1) << (63 - sh))) & (~0ull >> (64 - 2 * k));
+    const uint64_t x = funnel64(lo, hi, sh) & (~0ull >> (64 - 2 * k));
     return canonical ? kmer_finish<true>(x, k) : kmer_finish<false>(x, k);
 }
 

@@ -20,8 +20,8 @@
 //   3. orf_count     counts[tile] = the entries the tile's bounds emit;
 //   4. counted_scan
 //   5. orf_write     a tile whose count is 0 returns at once; the others repeat pass 3 and store their entries in order.
-// Shape of a tile, as in find_kernels.hpp: lane j owns the 32 positions that start in word j of the tile; it reads that word and
-// the next (two look-ahead nucleotides).  The four sets (stops and starts of either strand, the reverse ones already composed
+// Shape of a tile, as in word_tile.hpp: lane j owns the 32 positions that start in word j of the tile; it reads that word and
+// the next (word_tile_pair: two look-ahead nucleotides).  The four sets (stops and starts of either strand, the reverse ones already composed
 // with the codon's reverse complement) are staged as a 64-entry table in LDS, one byte lane per set: eight look-ups shifted into
 // one accumulator give eight positions of all four masks.
 #pragma once
@@ -65,11 +65,6 @@ __device__ __forceinline__ uint32_t orf_combine(uint32_t a, uint32_t b, bool rev
     return (b >> 16) ? b : ((a & 0xFFFF0000u) | st);
 }
 
-// bit r set iff position i0 + r < x
-__device__ __forceinline__ uint32_t orf_below(uint64_t i0, uint64_t x) {
-    return x <= i0 ? 0u : (x - i0 >= 32 ? ~0u : (1u << (uint32_t)(x - i0)) - 1u);
-}
-
 // What a lane knows of its 32 positions: bit r of stops[s] / starts[s] = position i0 + r is a stop / a start of strand s.  The
 // three positions len-2 .. len are stops of every strand scanned: they close the top runs.
 struct OrfLane {
@@ -87,17 +82,7 @@ __device__ __forceinline__ OrfLane orf_lane(const OrfArgs& a, uint64_t tile, uin
     }
     const uint64_t w0 = tile * kOrfTileWords;
     uint64_t lo, hi;
-    if (w0 + kOrfTileWords + 1 <= a.words) {
-        const __amdgpu_buffer_rsrc_t rin = rsrc_of(a.in + w0 * 8, (uint32_t)(kOrfTileWords + 1) * 8);
-        const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, j * 8, 0, kNT));
-        lo = ((uint64_t)q.y << 32) | q.x;
-        hi = ((uint64_t)q.w << 32) | q.z;
-    } else {
-        const uint64_t* in64 = reinterpret_cast<const uint64_t*>(a.in);
-        const uint64_t w = w0 + j;
-        lo = w < a.words ? in64[w] : 0;
-        hi = w + 1 < a.words ? in64[w + 1] : 0;
-    }
+    word_tile_pair<kOrfTileWords>(a.in, a.words, w0, j, lo, hi);
     __syncthreads();
     const uint32_t d[3] = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi};
     uint32_t acc[4];
@@ -105,16 +90,13 @@ __device__ __forceinline__ OrfLane orf_lane(const OrfArgs& a, uint64_t tile, uin
     for (int g = 0; g < 4; ++g) {
         acc[g] = 0;
 #pragma unroll
-        for (int r = 8 * g + 7; r >= 8 * g; --r) {  // downward: position r of the group ends in bit r of each byte
-            const uint32_t sh = 2 * (r & 15);
-            const uint32_t w = sh ? __builtin_amdgcn_alignbit(d[(r >> 4) + 1], d[r >> 4], sh) : d[r >> 4];
-            acc[g] = (acc[g] << 1) | s_tab[w & 63u];
-        }
+        for (int r = 8 * g + 7; r >= 8 * g; --r)  // downward: position r of the group ends in bit r of each byte
+            acc[g] = (acc[g] << 1) | s_tab[window_dword(d, r) & 63u];
     }
     OrfLane L;
     L.i0 = (w0 + j) * 32;
     L.m3 = (2u * (uint32_t)(tile % 3) + 2u * j) % 3u;  // 8192 = 32 = 2 (mod 3)
-    const uint32_t valid = orf_below(L.i0, a.len - 2), ends = orf_below(L.i0, a.len + 1) & ~valid;
+    const uint32_t valid = codes_below(L.i0, a.len - 2), ends = codes_below(L.i0, a.len + 1) & ~valid;
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const int b = 16 * s;
@@ -184,11 +166,6 @@ __device__ __forceinline__ void orf_combine64(uint64_t& stop, uint64_t& start, u
     }
 }
 
-__device__ __forceinline__ uint64_t orf_shfl_up64(uint64_t v, int o) {
-    const uint32_t lo = __shfl_up((uint32_t)v, o, 64), hi = __shfl_up((uint32_t)(v >> 32), o, 64);
-    return ((uint64_t)hi << 32) | lo;
-}
-
 // pass 2: workgroup p scans pair p, kOrfCarryBlock tiles a round
 __global__ __launch_bounds__(kOrfCarryBlock) void orf_carry(const uint32_t* __restrict__ sums, uint64_t* __restrict__ carry, uint64_t n_tiles) {
     __shared__ uint64_t s_w[kOrfCarryBlock / 64][2];
@@ -205,7 +182,7 @@ __global__ __launch_bounds__(kOrfCarryBlock) void orf_carry(const uint32_t* __re
         uint64_t stop = own_stop, start = own_start;  // inclusive over the wave
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
-            uint64_t y_stop = orf_shfl_up64(stop, o), y_start = orf_shfl_up64(start, o);
+            uint64_t y_stop = shfl_up_u64(stop, o), y_start = shfl_up_u64(start, o);
             if (lane >= (uint32_t)o) {
                 orf_combine64(y_stop, y_start, stop, start, rev);
                 stop = y_stop;
@@ -216,7 +193,7 @@ __global__ __launch_bounds__(kOrfCarryBlock) void orf_carry(const uint32_t* __re
             s_w[wave][0] = stop;
             s_w[wave][1] = start;
         }
-        uint64_t e_stop = orf_shfl_up64(stop, 1), e_start = orf_shfl_up64(start, 1);  // exclusive
+        uint64_t e_stop = shfl_up_u64(stop, 1), e_start = shfl_up_u64(start, 1);  // exclusive
         if (lane == 0) e_stop = e_start = kOrfNone;
         __syncthreads();
         uint64_t b_stop = c_stop, b_start = c_start;  // everything in front of the wave
@@ -318,23 +295,15 @@ __device__ __forceinline__ void orf_tile(const OrfArgs& a, uint64_t first_tile) 
         }
     }
     const uint32_t c = (uint32_t)__popc(fm) + (uint32_t)__popc(rm);
-    const uint32_t n = wave_inclusive_sum(c, lane);  // lane order = position order
-    if (lane == 63) s_cnt[wave] = n;
+    const uint32_t n = tile_rank_post(c, s_cnt);  // lane order = position order
     if constexpr (WRITE) {
         if (j == 0) s_base = counted_tile_base(a.offs, a.counts, tile);
     }
     __syncthreads();
     if constexpr (!WRITE) {
-        if (j == 0) {
-            uint32_t total = 0;
-#pragma unroll
-            for (int q = 0; q < kOrfWaves; ++q) total += s_cnt[q];
-            a.counts[tile] = total;
-        }
+        if (j == 0) a.counts[tile] = tile_total<kOrfWaves>(s_cnt);
     } else {
-        uint64_t at = s_base + (n - c);
-#pragma unroll
-        for (int q = 0; q < kOrfWaves - 1; ++q) at += q < (int)wave ? s_cnt[q] : 0u;
+        uint64_t at = s_base + tile_before<kOrfWaves>(s_cnt, n - c);
         // the lane's entries by their bound, forward before reverse; recomputed for the few bounds that emit
         for (uint32_t any = fm | rm; any; any &= any - 1) {
             const uint32_t r = (uint32_t)__builtin_ctz(any);

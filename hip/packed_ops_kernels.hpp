@@ -19,6 +19,7 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
+#include "word_tile.hpp"
 
 namespace cnt {
 
@@ -29,23 +30,27 @@ __device__ __forceinline__ uint32_t diff_codes32(uint32_t a, uint32_t b) {  // #
     return __builtin_popcount((x | (x >> 1)) & 0x55555555u);
 }
 
-__device__ __forceinline__ uint64_t block_sum_to(uint64_t v, unsigned long long* dst) {
-    // wave reduce -> LDS -> one no-return atomic per workgroup
+// wave reduce -> LDS -> thread 0 alone runs last(the workgroup's sum)
+template <typename F>
+__device__ __forceinline__ void block_sum(uint64_t v, F&& last) {
     __shared__ unsigned long long part[kRedBlock / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = __shfl_down((uint32_t)v, off, 64), hi = __shfl_down((uint32_t)(v >> 32), off, 64);
-        v += ((uint64_t)hi << 32) | lo;
-    }
+    v = wave_sum_u64(v);
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
         uint64_t s = 0;
         for (unsigned w = 0; w < blockDim.x / 64; ++w) s += part[w];
-        if (s) (void)__hip_atomic_fetch_add(dst, (unsigned long long)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return s;
+        last(s);
     }
-    return 0;
+}
+// one no-return atomic per workgroup that has something to add; or the sum to partial[blockIdx.x], no atomic
+__device__ __forceinline__ void block_sum_to(uint64_t v, unsigned long long* dst) {
+    block_sum(v, [&](uint64_t s) {
+        if (s) (void)__hip_atomic_fetch_add(dst, (unsigned long long)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    });
+}
+__device__ __forceinline__ void block_sum_store(uint64_t v, unsigned long long* partial) {
+    block_sum(v, [&](uint64_t s) { partial[blockIdx.x] = s; });
 }
 
 // Where the 16-B vector v of workgroup b's tile lives.  Linear: tile b, vector v.  XCD-interleaved
@@ -71,23 +76,6 @@ __device__ __forceinline__ uint32_t vec_offset(uint64_t b, uint64_t n_tiles, uin
 }
 
 // Hamming distance over whole 16-B vectors (64 nt each); tile = kRedBlock*U vectors per workgroup.
-// block_sum_to's sibling: the workgroup's sum goes to partial[blockIdx.x], no atomic
-__device__ __forceinline__ void block_sum_store(uint64_t v, unsigned long long* partial) {
-    __shared__ unsigned long long part2[kRedBlock / 64];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const uint32_t lo = __shfl_down((uint32_t)v, off, 64), hi = __shfl_down((uint32_t)(v >> 32), off, 64);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    if ((threadIdx.x & 63) == 0) part2[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint64_t s = 0;
-        for (unsigned w = 0; w < blockDim.x / 64; ++w) s += part2[w];
-        partial[blockIdx.x] = s;
-    }
-}
-
 // second pass: a few workgroups add the n partial sums into *count (one atomic each; a single
 // workgroup took 35-60 us for the 10^5 partials of a 2^34-nt call, 3-4 % of the whole call)
 __global__ __launch_bounds__(kRedBlock) void sum_partials(const unsigned long long* __restrict__ partial, uint64_t n,
@@ -257,12 +245,6 @@ __global__ __launch_bounds__(kBlock) void complement_generic(const uint64_t* __r
     }
 }
 
-// reverse the order of the 32 two-bit codes of a word
-__device__ __forceinline__ uint64_t reverse_codes64(uint64_t x) {
-    x = __brevll(x);  // reverses bits: also swaps the two bits inside each code ...
-    return ((x >> 1) & 0x5555555555555555ull) | ((x & 0x5555555555555555ull) << 1);  // ... swap them back
-}
-
 // reverse complement: output word w holds nt 32w..32w+31 = complement of input nt len-1-32w-k.
 // One thread per output word; each reads a 64-bit window that straddles two input words.
 __global__ __launch_bounds__(kBlock) void reverse_complement_words(const uint64_t* __restrict__ in, uint64_t* __restrict__ out,
@@ -306,18 +288,14 @@ __global__ __launch_bounds__(BLOCK) void reverse_complement_tiles(const uint8_t*
     const __amdgpu_buffer_rsrc_t rout = rsrc_of(out + w0 * 8, TILE_W * 8);
     const uint32_t i = threadIdx.x;
     typedef unsigned int vu2 __attribute__((__vector_size__(8)));
-    const u32x4 q = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rin, (TILE_W - 2 - 2 * i) * 8, 0, kNT));
+    const vu4 q = __builtin_amdgcn_raw_buffer_load_b128(rin, (TILE_W - 2 - 2 * i) * 8, 0, kNT);
     const vu2 e = __builtin_amdgcn_raw_buffer_load_b64(rin, sh ? (TILE_W - 2 * i) * 8 : 0xFFFFFFF0u, 0, kNT);
-    const uint64_t wm = ((uint64_t)q.y << 32) | q.x;   // input word j-1
-    const uint64_t wj = ((uint64_t)q.w << 32) | q.z;   // input word j
+    uint64_t wm, wj;  // input words j-1 and j
+    u64_pair(q, wm, wj);
     const uint64_t wp = ((uint64_t)e[1] << 32) | e[0];  // input word j+1 (0 when sh == 0)
-    // branch-free: (x << 1) << (63 - sh) is x << (64 - sh) for sh = 2..62 and 0 for sh = 0.  With `if (sh)` around the two ORs
-    // the compiler sank the second load into the branch, BEHIND the first load's s_waitcnt: two dependent trips to memory per
-    // tile whenever len is not a multiple of 32 (tests/test_isa_digest.py now counts the loads in flight at the first wait).
-    const uint64_t win0 = (wj >> sh) | ((wp << 1) << (63 - sh)), win1 = (wm >> sh) | ((wj << 1) << (63 - sh));
-    const uint64_t o0 = reverse_codes64(win0) ^ 0xAAAAAAAAAAAAAAAAull, o1 = reverse_codes64(win1) ^ 0xAAAAAAAAAAAAAAAAull;
-    const u32x4 o = {(uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32)};
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vu4, o), rout, i * 16, 0, kSC0 | kSC1 | kNT);
+    // funnel64 is branch-free so that both loads are in flight before the first wait (word_tile.hpp)
+    const uint64_t o0 = reverse_codes64(funnel64(wj, wp, sh)) ^ 0xAAAAAAAAAAAAAAAAull, o1 = reverse_codes64(funnel64(wm, wj, sh)) ^ 0xAAAAAAAAAAAAAAAAull;
+    __builtin_amdgcn_raw_buffer_store_b128(pack_u64x2(o0, o1), rout, i * 16, 0, kSC0 | kSC1 | kNT);
 }
 
 // validity: count bytes outside the alphabet.  SWAR: zero byte in (x & 0xDF) ^ expect  <=> valid letter.

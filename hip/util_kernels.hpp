@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "codec2_kernels.hpp"
+#include "word_tile.hpp"
 
 namespace cnt {
 
@@ -72,16 +73,6 @@ __global__ __launch_bounds__(kBlock) void fill_random_acgtn(uint8_t* __restrict_
             out[i0 + k] = is_n ? (uint8_t)'N' : (uint8_t)(0x54474341u >> (8 * c));
         }
     }
-}
-
-__device__ __forceinline__ uint64_t wave_sum_u64(uint64_t v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        uint32_t lo = __shfl_down((uint32_t)v, off, 64);
-        uint32_t hi = __shfl_down((uint32_t)(v >> 32), off, 64);
-        v += ((uint64_t)hi << 32) | lo;
-    }
-    return v;
 }
 
 __global__ __launch_bounds__(kBlock) void checksum_words(const uint64_t* __restrict__ w, uint64_t first_word,

@@ -94,7 +94,10 @@ def test_constants_and_loops_quote_the_sources():
     assert ka.count("std::min<uint64_t>(n_tiles, (uint64_t)chip_info().cus * %d)" % KMER_GROUPS_PER_CU) == 2  # both launches
     assert "const uint64_t tn = t + gridDim.x, cur_lo = lo, cur_hi = hi;" in kk
     assert "if (tn < n_tiles) load(tn, lo, hi);" in kk  # walk(reread=False)
-    assert "if (w0 + kKmerCountTileWords + 1 <= words) {" in kk  # kmer_tile_is_fast
+    # kmer_tile_is_fast: the shared loader's condition, which kmer_count instantiates at its tile size with BACK = 0 (the default)
+    wt = _src("hip", "word_tile.hpp")
+    assert "template <uint64_t TILE_WORDS, uint64_t BACK = 0>" in wt and wt.count("if (w0 >= BACK && w0 - BACK + TILE_WORDS + 1 <= words) {") == 1
+    assert "word_tile_pair<kKmerCountTileWords>(in, words, t * kKmerCountTileWords, j, lo, hi);" in kk
 
 
 # ---- the model of the walk ------------------------------------------------------------------------------------------------

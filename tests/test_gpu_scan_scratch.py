@@ -62,8 +62,8 @@ CARVING = {
 # The stores into the scratch, all there are:
 #   offs[0 .. groups)        hip/counted_output.hpp counted_scan        "if (g < n_groups) offs[g] = before;"
 #   counts[0 .. n_tiles)     hip/minimizer_kernels.hpp minimizer_tiles  "counts[tile] = (uint32_t)c;"
-#                            hip/find_kernels.hpp find_tile             "counts[tile] = total;"
-#                            hip/orf_kernels.hpp orf_tile               "a.counts[tile] = total;"
+#                            hip/find_kernels.hpp find_tile             "if (j == 0) counts[tile] = tile_total<kFindWaves>(s_cnt);"
+#                            hip/orf_kernels.hpp orf_tile               "if (j == 0) a.counts[tile] = tile_total<kOrfWaves>(s_cnt);"
 #   sums[p][0 .. n_tiles)    hip/orf_kernels.hpp orf_summary            "if (threadIdx.x < (both ? kOrfPairs : 3)) {" ... "a.sums[p * a.n_tiles + tile] = v;"
 #   carry[p][0 .. 2)[0 .. n_tiles)  hip/orf_kernels.hpp orf_carry       "uint64_t* out_stop = carry + 2ull * p * n_tiles;" "uint64_t* out_start = out_stop + n_tiles;"
 #                            "if (t < n_tiles) {" "out_stop[t] = f_stop;" "out_start[t] = f_start;", p = blockIdx.x of the launch
@@ -73,8 +73,8 @@ CARVING = {
 STORES = {
     "counted_output.hpp": ["if (g < n_groups) offs[g] = before;"],
     "minimizer_kernels.hpp": ["counts[tile] = (uint32_t)c;"],
-    "find_kernels.hpp": ["counts[tile] = total;"],
-    "orf_kernels.hpp": ["a.counts[tile] = total;", "if (threadIdx.x < (both ? kOrfPairs : 3)) {", "a.sums[p * a.n_tiles + tile] = v;",
+    "find_kernels.hpp": ["if (j == 0) counts[tile] = tile_total<kFindWaves>(s_cnt);"],
+    "orf_kernels.hpp": ["if (j == 0) a.counts[tile] = tile_total<kOrfWaves>(s_cnt);", "if (threadIdx.x < (both ? kOrfPairs : 3)) {", "a.sums[p * a.n_tiles + tile] = v;",
                         "uint64_t* out_stop = carry + 2ull * p * n_tiles;", "uint64_t* out_start = out_stop + n_tiles;", "out_stop[t] = f_stop;",
                         "out_start[t] = f_start;", "uint64_t* carry;           // [kOrfPairs][2][n_tiles]: stop, start"],
     "orf_abi.inc": ["hipLaunchKernelGGL(orf_carry, dim3(both ? kOrfPairs : 3), dim3(kOrfCarryBlock), 0, s, sums, carry, n_tiles);"],

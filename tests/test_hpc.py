@@ -491,6 +491,28 @@ def test_gpu_lengths_and_padding_both_tiers(L):
                         check_host(L, s, words=w, tag=(last, mean, pad))
 
 
+@gpu
+@pytest.mark.parametrize("n_len", [TILE, 2 * TILE - 32, 2 * TILE, 2 * TILE + 1, 3 * TILE + 1])
+def test_gpu_word_in_front_at_the_fast_path_boundary(n_len):
+    """A tile takes the 16-B loads iff it is not tile 0 and the 257 words from the one in FRONT of it on all exist (hip/word_tile.hpp,
+    word_tile_pair with BACK = 1).  T: tile 0 alone, guarded.  2T - 32, 2T, 2T + 1: tile 1's last word is one past, at and inside
+    the input.  3T + 1: fast tiles between a guarded first and a guarded last.  Inputs in which the word in front decides a kept
+    position: one base throughout (only position 0 is kept, in every tile), and runs that end exactly at the last code of word 255
+    and of word 256 (and of the same words of every later tile), so that word 256 / 257 begins a run."""
+    rng = np.random.default_rng(30)
+    runs = run_lengths_seq(rng, n_len, 3)
+    for t in range(TILE, n_len, TILE):
+        for lo, hi, code in ((t - 7, t, C), (t, t + 32, G), (t + 32, t + 37, T)):
+            runs[lo:min(hi, n_len)] = code
+    for name, s in (("one base", np.full(n_len, T, dtype=np.uint8)), ("runs to the word edges", runs)):
+        for with_pos in (True, False):
+            n = check_dev(s, with_pos=with_pos, in_phase=int(with_pos), tag=(name,))
+            assert name != "one base" or n == 1
+    kept = np_hpc(runs)[1].astype(np.int64)
+    for t in range(TILE, n_len, TILE):
+        assert t in kept and (t + 32 in kept or t + 32 >= n_len) and not ((kept > t) & (kept < min(t + 32, n_len))).any()
+
+
 def _seam_cases(rng):
     """(name, codes): runs at every seam of the tile shape"""
     n_len = 5 * TILE + 1
