@@ -429,10 +429,15 @@ def _unary_dev(fn, bits, length, out):
 
 
 def complement_dev(bits, length, out=None):
+    """Device tier of complement_hip, enqueued on torch's current stream: the [:words_for(length)] view of an int64 tensor (`out`
+    if given).  In place works: complement_dev(x, n, out=x) overwrites x with its complement (out and bits at the SAME address);
+    an `out` that overlaps `bits` in any other way is refused with CNT_EINVAL."""
     return _unary_dev(lib().cnt_complement_dev, bits, length, out)
 
 
 def reverse_complement_dev(bits, length, out=None):
+    """Device tier of reverse_complement_hip, enqueued on torch's current stream.  Not in place: an `out` that shares any word
+    with `bits` (out=bits included) is refused with CNT_EINVAL."""
     return _unary_dev(lib().cnt_reverse_complement_dev, bits, length, out)
 
 

@@ -113,7 +113,7 @@ inline void counted_scan_enqueue(const CountedScratch& w, uint64_t n_tiles, void
 // The argument checks every tier of the three calls ends with, before any device work (the call's own parameter checks come first
 // and "nothing to compute" returns before these): bits, the required outputs and count present and 8-B aligned, an optional output
 // aligned when present, and no two of them sharing memory -- the input at its words, the outputs at the min(most, out_cap) entries
-// that can be written.
+// that can be written, the count at its 8 bytes.  counted_work() is the same rule for the device tier's scratch.
 struct CountedOut {
     const void* p;
     bool required;
@@ -123,12 +123,24 @@ inline int counted_args(const void* bits, size_t len, std::initializer_list<Coun
     for (const CountedOut& o : outs)
         if ((o.required && !o.p) || !aligned(o.p, 8)) return CNT_EINVAL;
     const size_t in_bytes = cnt_words_for(len) * 8, out_bytes = std::min<uint64_t>(most, out_cap) * 8;
+    if (overlaps(count, 8, bits, in_bytes)) return CNT_EINVAL;
     for (const CountedOut* o = outs.begin(); o != outs.end(); ++o) {
         if (!o->p) continue;
-        if (overlaps(bits, in_bytes, o->p, out_bytes)) return CNT_EINVAL;
+        if (overlaps(bits, in_bytes, o->p, out_bytes) || overlaps(count, 8, o->p, out_bytes)) return CNT_EINVAL;
         for (const CountedOut* e = outs.begin(); e != o; ++e)
             if (e->p && overlaps(e->p, out_bytes, o->p, out_bytes)) return CNT_EINVAL;
     }
+    return CNT_OK;
+}
+
+// The device tier's scratch, behind counted_args: present, at least the `need` bytes the call's *_work_bytes query answers, and
+// those bytes (not what the caller lent beyond them) sharing none with the input words, an output or the count.
+inline int counted_work(const void* d_work, size_t work_bytes, size_t need, const void* bits, size_t len, std::initializer_list<const void*> outs,
+                        uint64_t most, size_t out_cap, const void* count) {
+    if (work_bytes < need || !d_work) return CNT_EINVAL;
+    if (overlaps(d_work, need, bits, cnt_words_for(len) * 8) || overlaps(d_work, need, count, 8)) return CNT_EINVAL;
+    for (const void* o : outs)
+        if (o && overlaps(d_work, need, o, std::min<uint64_t>(most, out_cap) * 8)) return CNT_EINVAL;
     return CNT_OK;
 }
 

@@ -22,6 +22,10 @@ int extract_args(const void* bits, size_t len, const void* start, bool want_star
     if (overlaps(out, out_bytes, bits, cnt_words_for(len) * 8) || (want_start && overlaps(out, out_bytes, start, n * 8)) ||
         (info && overlaps(out, out_bytes, info, n * 8)))
         return CNT_EINVAL;
+    // the counter of rejected regions is written too
+    if (rejected && (overlaps(rejected, 8, out, out_bytes) || overlaps(rejected, 8, bits, cnt_words_for(len) * 8) ||
+                     (want_start && overlaps(rejected, 8, start, n * 8)) || (info && overlaps(rejected, 8, info, n * 8))))
+        return CNT_EINVAL;
     *rec_words = R;
     return CNT_OK;
 }

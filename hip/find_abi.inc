@@ -60,7 +60,7 @@ int cnt_find_pattern_dev(const void* d_bits, size_t len, uint64_t pattern, unsig
     CNT_TRY(find_args(d_bits, len, pattern, k, wildcards, max_mismatches, flags, d_pos, d_info, out_cap, d_count, &m, &most));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (m == 0) return counted_empty_dev(d_count, s);
-    if (work_bytes < find_work_bytes(m) || !d_work) return CNT_EINVAL;
+    CNT_TRY(counted_work(d_work, work_bytes, find_work_bytes(m), d_bits, len, {d_pos, d_info}, most, out_cap, d_count));
     const uint64_t n_tiles = (m + kFindTile - 1) / kFindTile;
     const CountedScratch work = counted_carve(d_work, n_tiles);
     const uint8_t* in = static_cast<const uint8_t*>(d_bits);

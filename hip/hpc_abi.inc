@@ -19,6 +19,7 @@ int hpc_args(const void* bits, size_t len, unsigned flags, const void* out, cons
     if (!bits || !out || !count || !aligned(bits, 8) || !aligned(out, 8) || !aligned(count, 8) || !aligned(pos, 8)) return CNT_EINVAL;
     const size_t in_bytes = cnt_words_for(len) * 8, out_bytes = cnt_words_for(*cap) * 8, pos_bytes = pos ? *cap * 8 : 0;
     if (overlaps(bits, in_bytes, out, out_bytes) || overlaps(bits, in_bytes, pos, pos_bytes) || overlaps(out, out_bytes, pos, pos_bytes)) return CNT_EINVAL;
+    if (overlaps(count, 8, bits, in_bytes) || overlaps(count, 8, out, out_bytes) || overlaps(count, 8, pos, pos_bytes)) return CNT_EINVAL;
     return CNT_OK;
 }
 
@@ -39,7 +40,11 @@ int cnt_hpc_dev(const void* d_bits, size_t len, unsigned flags, void* d_out, voi
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (len == 0) return counted_empty_dev(d_count, s);
     const uint64_t n_tiles = hpc_tiles(len);
-    if (work_bytes < counted_scratch_bytes(n_tiles) || !d_work) return CNT_EINVAL;
+    const size_t need = counted_scratch_bytes(n_tiles);  // the scratch at the query's size, against everything else of the call
+    if (work_bytes < need || !d_work) return CNT_EINVAL;
+    if (overlaps(d_work, need, d_bits, cnt_words_for(len) * 8) || overlaps(d_work, need, d_out, cnt_words_for(cap) * 8) ||
+        overlaps(d_work, need, d_pos, d_pos ? cap * 8 : 0) || overlaps(d_work, need, d_count, 8))
+        return CNT_EINVAL;
     const CountedScratch work = counted_carve(d_work, n_tiles);
     const HpcArgs a = {static_cast<const uint8_t*>(d_bits), cnt_words_for(len), len, n_tiles, work.counts, work.offs, static_cast<uint64_t*>(d_out),
                        static_cast<uint64_t*>(d_pos), cap};

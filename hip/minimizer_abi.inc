@@ -41,7 +41,7 @@ int cnt_minimizers_dev(const void* d_bits, size_t len, unsigned k, unsigned w, u
     CNT_TRY(minimizer_args(d_bits, len, k, w, flags, d_pos, d_val, out_cap, d_count, &n_win));
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (n_win == 0) return counted_empty_dev(d_count, s);
-    if (work_bytes < minimizer_work_bytes(n_win) || !d_work) return CNT_EINVAL;
+    CNT_TRY(counted_work(d_work, work_bytes, minimizer_work_bytes(n_win), d_bits, len, {d_pos, d_val}, n_win, out_cap, d_count));
     const uint64_t n_tiles = (n_win + kMinTile - 1) / kMinTile;
     const CountedScratch work = counted_carve(d_work, n_tiles);
     const uint64_t* in = static_cast<const uint64_t*>(d_bits);

@@ -50,7 +50,7 @@ int cnt_orfs_dev(const void* d_bits, size_t len, uint64_t stops, uint64_t starts
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (len < 3) return counted_empty_dev(d_count, s);
     const uint64_t n_tiles = orf_tiles(len);
-    if (work_bytes < orf_work_bytes(n_tiles) || !d_work) return CNT_EINVAL;
+    CNT_TRY(counted_work(d_work, work_bytes, orf_work_bytes(n_tiles), d_bits, len, {d_pos, d_length, d_info}, most, out_cap, d_count));
     const CountedScratch work = counted_carve(d_work, n_tiles);
     uint32_t* sums = static_cast<uint32_t*>(work.behind);
     uint64_t* carry = reinterpret_cast<uint64_t*>(sums + n_tiles * kOrfPairs);

@@ -13,9 +13,11 @@ extern "C" {
 int cnt_hamming_dev(const void* d_a, const void* d_b, size_t len, void* d_count, void* stream) {
     if (len == 0) return CNT_OK;
     if (!d_a || !d_b || !d_count || !aligned(d_a, 8) || !aligned(d_b, 8) || !aligned(d_count, 8)) return CNT_EINVAL;
+    const uint64_t words = cnt_words_for(len);
+    // the counter is written: it shares no byte with either stream (a and b are only read and may overlap each other freely)
+    if (overlaps(d_count, 8, d_a, words * 8) || overlaps(d_count, 8, d_b, words * 8)) return CNT_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned long long* count = static_cast<unsigned long long*>(d_count);
-    const uint64_t words = cnt_words_for(len);
     uint64_t done_words = 0;
     constexpr int U = 2;
     constexpr uint64_t kTileWords = (uint64_t)kRedBlock * U * 2;  // 16-B vectors = 2 words each
@@ -93,8 +95,11 @@ int cnt_hamming_dev(const void* d_a, const void* d_b, size_t len, void* d_count,
 int cnt_complement_dev(const void* d_bits, size_t len, void* d_out, void* stream) {
     if (len == 0) return CNT_OK;
     if (!d_bits || !d_out || !aligned(d_bits, 8) || !aligned(d_out, 8)) return CNT_EINVAL;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t words = cnt_words_for(len);
+    // exactly in place is fine: every lane stores only the words it loaded.  Any other overlap races one workgroup's loads
+    // against another's stores.
+    if (d_bits != d_out && overlaps(d_bits, words * 8, d_out, words * 8)) return CNT_EINVAL;
+    hipStream_t s = static_cast<hipStream_t>(stream);
     uint64_t done_words = 0;
     constexpr int B = 256, U = 1;
     constexpr uint64_t kTileWords = (uint64_t)B * U * 2;
@@ -125,8 +130,9 @@ int cnt_complement_dev(const void* d_bits, size_t len, void* d_out, void* stream
 
 int cnt_reverse_complement_dev(const void* d_bits, size_t len, void* d_out, void* stream) {
     if (len == 0) return CNT_OK;
-    if (!d_bits || !d_out || !aligned(d_bits, 8) || !aligned(d_out, 8) || d_bits == d_out) return CNT_EINVAL;  // not in place
+    if (!d_bits || !d_out || !aligned(d_bits, 8) || !aligned(d_out, 8)) return CNT_EINVAL;
     const uint64_t words = cnt_words_for(len);
+    if (overlaps(d_bits, words * 8, d_out, words * 8)) return CNT_EINVAL;  // not in place, and not shifted onto itself either
     hipStream_t s = static_cast<hipStream_t>(stream);
     constexpr int B = 256;
     constexpr uint64_t kTileWords = (uint64_t)B * 2;
@@ -159,6 +165,7 @@ int cnt_validate_dev(const void* d_n, size_t n_len, unsigned flags, void* d_inva
     if (flags & ~CNT_ALLOW_N) return CNT_EINVAL;
     if (n_len == 0) return CNT_OK;
     if (!d_n || !d_invalid_count || !aligned(d_invalid_count, 8)) return CNT_EINVAL;
+    if (overlaps(d_invalid_count, 8, d_n, n_len)) return CNT_EINVAL;  // the counter is written: not inside the bytes it counts
     hipStream_t s = static_cast<hipStream_t>(stream);
     unsigned long long* count = static_cast<unsigned long long*>(d_invalid_count);
     const bool allow_n = (flags & CNT_ALLOW_N) != 0;
@@ -232,10 +239,12 @@ int cnt_validate_dev(const void* d_n, size_t n_len, unsigned flags, void* d_inva
 // ---- host tier: host_call (cute_nt.hip) ---------------------------------------------------
 int cnt_hamming(const uint64_t* a, const uint64_t* b, size_t len, uint64_t* distance) {
     if (!distance) return CNT_EINVAL;
+    const size_t bytes = cnt_words_for(len) * 8;
+    // a result inside a stream it is computed from: refused before anything is written, *distance included
+    if ((a && overlaps(distance, 8, a, bytes)) || (b && overlaps(distance, 8, b, bytes))) return CNT_EINVAL;
     *distance = 0;
     if (len == 0) return CNT_OK;
     if (!a || !b) return CNT_EINVAL;
-    const size_t bytes = cnt_words_for(len) * 8;
     return host_call({{a, bytes, Dir::in}, {b, bytes, Dir::in}}, 16, distance, true,
                      [&](void* const* d, void* count, hipStream_t s) { return cnt_hamming_dev(d[0], d[1], len, count, s); });
 }
@@ -255,6 +264,7 @@ int cnt_reverse_complement(const uint64_t* bits, size_t len, uint64_t* out) {
 
 int cnt_validate(const uint8_t* n, size_t n_len, unsigned flags, uint64_t* invalid) {
     if (!invalid) return CNT_EINVAL;
+    if (n && overlaps(invalid, 8, n, n_len)) return CNT_EINVAL;  // before anything is written, *invalid included
     *invalid = 0;
     if (flags & ~CNT_ALLOW_N) return CNT_EINVAL;
     if (n_len == 0) return CNT_OK;

@@ -21,8 +21,9 @@
  *   - caller-allocated outputs.  The library never keeps a caller pointer after
  *     return and never frees caller memory.
  *   - inputs and outputs of one call do not share memory (the reference borrows
- *     `&[u8]` / `&[u64]` and returns a fresh Vec, n_to_bits.rs:34,51): a codec call
- *     whose input range overlaps one of its output ranges is CNT_EINVAL, in every tier.
+ *     `&[u8]` / `&[u64]` and returns a fresh Vec, n_to_bits.rs:34,51): a call in which a
+ *     range it writes overlaps another of its ranges is CNT_EINVAL, in every tier (the
+ *     packed-domain section states the rule in full, with its two exceptions).
  *   - thread-safe and re-entrant: per-thread HIP stream + scratch (the
  *     reference's functions are pure and callable from any thread).
  *   - layout (n_to_bits.rs:39-42,61-64): nucleotide i lives in word i>>5 at bit
@@ -44,7 +45,8 @@ extern "C" {
 
 /* ---- status codes ---------------------------------------------------------- */
 #define CNT_OK 0
-#define CNT_EINVAL 1 /* NULL pointer with a non-zero size, bad flag, bad ndev, input overlapping output */
+#define CNT_EINVAL 1 /* NULL pointer with a non-zero size, bad alignment, bad flag, bad ndev, a written buffer of the
+                        call overlapping another of its buffers */
 #define CNT_ECAP 2   /* output capacity < ceil(n_len/32) (or /27) words */
 #define CNT_ELEN 3   /* decode: len > 32*words (27*words) -- the reference's
                         panic "The length is greater than the number of
@@ -355,10 +357,39 @@ int cnt_dev_sync(void *stream);
  * cnt_set_tuning("reduce_persistent", 0); only that form allocates, and cnt_get_tuning("reduce_fallbacks")
  * counts the calls in which its allocation failed.)
  * Host tier: synchronous.
+ *
+ * SHARED MEMORY, every call of this section, both tiers:
+ *   1. A buffer a call WRITES shares no byte with any other buffer of that call.  Written are: an output, a count the call
+ *      sets, a counter it adds to, and its d_work.  The extents are the ones each call states: cnt_words_for(len) input words,
+ *      the min(most, out_cap) entries of a counted output that can be written, cnt_hpc's footprint, the M bytes of a
+ *      translation, the 4^k entries of a table; a count or a counter is 8 bytes; d_work has the extent the call's *_work_bytes
+ *      query answers, not what the caller lent beyond it.  A violation is CNT_EINVAL before any device work (nothing is
+ *      written, a host count included when it is the buffer at fault); in each call's order of checks it stands where that
+ *      call's overlap check stands.
+ *   2. Buffers a call only READS may overlap each other in any way: cnt_hamming(a, a) and cnt_hamming(a, a + 1 word) are legal.
+ *      (cnt_translate's table is copied at entry and is no buffer in this sense.)
+ *   3. Two exceptions.  cnt_complement_dev with d_out == d_bits EXACTLY is legal: every lane stores only the words it loaded, so
+ *      a pipeline short of memory complements in place; any other overlap of the two is CNT_EINVAL.  And the HOST tier of
+ *      complement and reverse complement accepts an output that overlaps its input in any way: such a call is staged
+ *      ("pinned caller memory" above), and the result is that of the original input.
+ * Buffers that merely touch (one ends where the other begins) share no byte and are fine.
+ *
  *   hamming             #{ i < len : code_a(i) != code_b(i) }
+ *                       Errors (len > 0): a NULL or not 8-B aligned a, b or counter; the counter overlapping a or b: CNT_EINVAL.
+ *                       Host tier: a NULL distance is CNT_EINVAL at every len; otherwise *distance = 0 before the other checks,
+ *                       except that a distance overlapping a or b is refused without being written.
  *   complement          A<->T, C<->G
+ *                       Errors (len > 0): a NULL or not 8-B aligned bits or out; device tier: out overlapping bits other than
+ *                       out == bits (in place): CNT_EINVAL.  Host tier: any overlap is legal.
  *   reverse_complement  out(i) = complement(in(len-1-i)); not in place
- *   validate            #{ bytes outside ACGTUacgtu }, with CNT_ALLOW_N also N/n are legal */
+ *                       Errors (len > 0): a NULL or not 8-B aligned bits or out; device tier: out overlapping bits in any
+ *                       way, out == bits included: CNT_EINVAL.  Host tier: any overlap is legal.
+ *   validate            #{ bytes outside ACGTUacgtu }, with CNT_ALLOW_N also N/n are legal
+ *                       Errors: an unknown flag, even at n_len == 0; n_len > 0: a NULL n, a NULL or not 8-B aligned counter, the
+ *                       counter overlapping the n_len bytes: CNT_EINVAL.  Host tier: a NULL invalid is CNT_EINVAL at every
+ *                       n_len; otherwise *invalid = 0 before the other checks, except that an invalid overlapping n is refused
+ *                       without being written.
+ * len == 0 (n_len == 0): CNT_OK whatever the pointers are (validate: after the flag check). */
 #define CNT_ALLOW_N 0x2u
 int cnt_hamming_dev(const void *d_a, const void *d_b, size_t len, void *d_count, void *stream);
 int cnt_complement_dev(const void *d_bits, size_t len, void *d_out, void *stream);
@@ -425,8 +456,9 @@ int cnt_kmer_counts(const uint64_t *bits, size_t len, unsigned k, unsigned flags
  *           info is not NULL, info[j] = the hit's mismatch count, plus CNT_FIND_REVERSE for a reverse-strand hit.
  * Input bits beyond len are ignored.
  * Errors, before any device work: k == 0, k > 32, pattern bits at or above 2k, wildcard bits at or above k, max_mismatches > k,
- * an unknown flag; when m > 0: a NULL or not 8-B aligned bits, pos or count, an info not 8-B aligned, pos or info overlapping
- * the input words or each other; work_bytes below the query's answer: CNT_EINVAL.  m == 0: CNT_OK with the count set to 0
+ * an unknown flag; when m > 0: a NULL or not 8-B aligned bits, pos or count, an info not 8-B aligned, pos, info or count overlapping
+ * the input words or each other; d_work NULL, work_bytes below the query's answer, or the query's bytes of d_work overlapping
+ * the input words, pos, info or count: CNT_EINVAL.  m == 0: CNT_OK with the count set to 0
  * (when a count pointer is given).
  * cnt_find_pattern_work_bytes: the device scratch cnt_find_pattern_dev needs (0 when m == 0; d_work may then be NULL).
  * Device tier: enqueue-only (three kernels: count per tile of 8192 windows, scan, write; no allocation, no synchronisation,
@@ -474,7 +506,8 @@ int cnt_find_pattern(const uint64_t *bits, size_t len, uint64_t pattern, unsigne
  * Empty work: n == 0 or region_len == 0 (sub_len == 0): CNT_OK, nothing is read or written (the host tier still sets
  *   *rejected = 0).
  * Errors, before any device work: an unknown flag; a NULL or not 8-B aligned bits, start or out, an info or rejected not 8-B
- *   aligned, out overlapping bits, start or info, a region of 2^45 nt or more: CNT_EINVAL; n * R overflowing size_t or
+ *   aligned, out overlapping bits, start or info, rejected overlapping out, bits, start or info, a region of 2^45 nt or more:
+ *   CNT_EINVAL; n * R overflowing size_t or
  *   out_words < n*R: CNT_ECAP.
  * Device tier: enqueue-only (no allocation, no synchronisation, no scratch, capturable in a graph), pointers at any 8-B phase, len
  *   and start may exceed 2^32.  One thread per output word (a gather: two dependent loads per word) for records below 512 words;
@@ -568,8 +601,9 @@ int cnt_translate(const uint64_t *bits, size_t len, size_t start, size_t sub_len
  * The checks, in this order and all before any device work:
  *   1. stops == 0 or an unknown flag: CNT_EINVAL, even without work
  *   2. len < 3 (no codon): CNT_OK with the count set to 0 (when a count pointer is given)
- *   3. a NULL or not 8-B aligned bits, pos, length or count, an info not 8-B aligned, pos, length or info overlapping the input
- *      words or each other; d_work NULL or work_bytes below the query's answer: CNT_EINVAL
+ *   3. a NULL or not 8-B aligned bits, pos, length or count, an info not 8-B aligned, pos, length, info or count overlapping the
+ *      input words or each other; d_work NULL, work_bytes below the query's answer, or the query's bytes of d_work overlapping
+ *      the input words, an output or count: CNT_EINVAL
  * cnt_orfs_work_bytes: the device scratch cnt_orfs_dev needs; it depends on len only (0 when len < 3; d_work may then be
  *   NULL), about 125 B per 8192 nt.
  * Device tier: enqueue-only (no allocation, no synchronisation, capturable in a graph), d_bits at any 8-B phase, len up to
@@ -617,8 +651,9 @@ int cnt_orfs(const uint64_t *bits, size_t len, uint64_t stops, uint64_t starts, 
  *   1. flags != 0 (none is defined): CNT_EINVAL, even without work; cnt_hpc_work_bytes: a NULL bytes
  *   2. len == 0: CNT_OK with the count set to 0 (when a count pointer is given), nothing else is touched
  *   3. a NULL or not 8-B aligned bits, out or count, a pos not 8-B aligned, the footprint of out or pos[0 .. min(len, out_cap))
- *      overlapping the input words or each other (no in-place call: the input is read twice); d_work NULL or work_bytes below
- *      the query's answer: CNT_EINVAL
+ *      or count overlapping the input words or each other (no in-place call: the input is read twice); d_work NULL, work_bytes
+ *      below the query's answer, or the query's bytes of d_work overlapping the input words, the footprint, pos or count:
+ *      CNT_EINVAL
  * cnt_hpc_work_bytes: the device scratch cnt_hpc_dev needs; it depends on len only (0 when len == 0), about 5 B per 8192 nt.
  * Device tier: enqueue-only (no allocation, no synchronisation, capturable in a graph), d_bits and d_out at any 8-B phase, len
  *   up to 2^36, d_work any caller scratch that nobody needs zeroed.  *d_count (device u64) is SET to n whether or not the
@@ -657,8 +692,9 @@ int cnt_hpc(const uint64_t *bits, size_t len, unsigned flags, uint64_t *out, uin
  * Not minimap2's minimizers: another hash, palindromic k-mers (fwd == rc, even k) are not skipped, and there are no
  * partial windows at either end.
  * Errors, before any device work: k, w or flags out of range; when W > 0: a NULL or not 8-B aligned bits, pos or count, a
- * val not 8-B aligned, pos or val overlapping the input words or each other; work_bytes below the query's answer:
- * CNT_EINVAL.  W == 0: CNT_OK with the count set to 0 (when a count pointer is given).
+ * val not 8-B aligned, pos, val or count overlapping the input words or each other; d_work NULL, work_bytes below the query's
+ * answer, or the query's bytes of d_work overlapping the input words, pos, val or count: CNT_EINVAL.  W == 0: CNT_OK with
+ * the count set to 0 (when a count pointer is given).
  * cnt_minimizers_work_bytes: the device scratch cnt_minimizers_dev needs (0 when W == 0; d_work may then be NULL).
  * Device tier: enqueue-only (three kernels, no allocation, capturable in a graph), pointers at any 8-B phase, d_work any
  *   caller scratch that nobody needs zeroed.  *d_count (device u64) is SET to n -- unlike the counters of cnt_hamming_dev and

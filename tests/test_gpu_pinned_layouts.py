@@ -377,7 +377,7 @@ def test_host_call_lane_rules(oracle, n_len):
     d = PackedData(oracle, n_len)
     L = _lib()
     words = d.a.size
-    for kind in ("alloc1", "reg_interior", "reg_exact"):
+    for kind in ("alloc1", "reg_interior", "reg_exact", "plain"):  # three pinned layouts and ordinary, pageable memory
         # hamming(a, a): the same buffer twice, both Dir::in
         sides = _sides([(kind, (words + 1) * 8, 8)], (n_len, kind))
         (s,) = sides
