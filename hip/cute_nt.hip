@@ -155,8 +155,7 @@ inline unsigned generic_grid(uint64_t items, unsigned block = kBlock) {
 // n_tiles one-workgroup tiles of `block` threads in launches of at most max_tiles_per_launch(block): launch(first, n) for each
 template <typename F>
 void split_launches(uint64_t n_tiles, int block, F&& launch) {
-    const uint64_t per_launch = max_tiles_per_launch(block);
-    for (uint64_t first = 0; first < n_tiles; first += per_launch) launch(first, std::min(per_launch, n_tiles - first));
+    for_each_launch(n_tiles, max_tiles_per_launch(block), [&](uint64_t first, uint64_t n, bool) { launch(first, n); });
 }
 
 // the end of a synchronous call on stream s: drains it whatever rc is, and reports rc, else the drain's own status

@@ -416,8 +416,9 @@ int decode2_dev(const void* d_bits, size_t words, size_t len, void* d_out, unsig
         return CNT_OK;
     }
 #ifdef CNT_LAB_VARIANTS
-    if (tune_decode2() >= kFirstPageDecode2Variant && tune_decode2() < kEndPageDecode2Variant) {
-        const int rc = launch_decode2_page(tune_decode2(), bits, used_words, out, len, s);
+    const int v = tune_decode2();
+    if (v >= 0 && v < kNumDecode2Variants && kDecode2Variants[v].pages) {
+        const int rc = launch_decode2_page(v, bits, used_words, out, len, s);
         if (rc > 0) return CNT_EINVAL;
         if (rc < 0) generic(len, 0, used_words);
         HIP_TRY(hipGetLastError());

@@ -2,6 +2,7 @@
 include/cute_nt.h declares, and its argument validation mirrors the reference's error
 behaviour.  No compute is launched here."""
 import ctypes
+import hashlib
 import os
 import re
 
@@ -219,20 +220,35 @@ def test_product_build_has_no_kernel_selection(L):
         devutil.set_tuning("encode", 0)
 
 
+# the lab build's four variant tables: (rows, sha256 of the names joined by newlines).  A variant's index is its identity (the
+# tuning keys, bench/ and every "variant N" in profiles/ select by it) and its name spells the kernel it launches: the pair pins
+# both, so that a row moved, dropped, added in the middle or renamed fails
+VARIANT_NAMES = {
+    "encode": (28, "152c7d7d84f1a56d57355f635ed353819eda531d96ce3aa672a64519de0f6ab9"),
+    "decode": (46, "e94de8364e8df5bb97faf05d8d338a9feab28a0a431660303a84eb8e4367cced"),
+    "encode2": (52, "2055ef64c532409000e916e777719031980b1a19443151890999aaf2d7393459"),
+    "decode2": (73, "e1b4abeced7cb500ca6ee2594601db8bc585f9b0c222b06c2cfbf09f142a0169"),
+}
+
+
 def test_tuning_knobs(L, lab_build):
     from cute_nucleotides_amd import _lib, devutil
 
     L = _lib.lib()  # the lab build
-    for key in ("encode", "decode"):
+    for key in ("encode", "decode", "encode2", "decode2"):
         old = devutil.get_tuning(key)
         assert old == 0  # the shipped default
         n = devutil.get_tuning(key + "_variants")
         assert n >= 2
         try:
+            names = []
             for v in range(n):
                 devutil.set_tuning(key, v)
                 assert devutil.get_tuning(key) == v
                 assert L.cnt_tuning_name(key.encode(), v)
+                names.append(L.cnt_tuning_name(key.encode(), v).decode())
+            # every entry in profiles/ that says "variant 17" means this index and this name: a row moved, dropped or renamed fails here
+            assert (n, hashlib.sha256("\n".join(names).encode()).hexdigest()) == VARIANT_NAMES[key], key
             assert L.cnt_set_tuning(key.encode(), n) == 1
             assert L.cnt_set_tuning(key.encode(), -1) == 1
             assert L.cnt_tuning_name(key.encode(), n) is None

@@ -287,12 +287,21 @@ def kmer_plan(out_ptr, n_len, k, launch_tiles=KMER_HW_LAUNCH_TILES):
 
 
 def assert_split_launches_by_max_tiles_per_launch():
-    """cute_nt.hip's split_launches, which the launchers call with their block: launches of max_tiles_per_launch(block) tiles"""
+    """cute_nt.hip's split_launches, which the launchers call with their block: launches of max_tiles_per_launch(block) tiles,
+    taken in order by codec2_launch.hpp's for_each_launch (the one loop over launches), the last one the remainder"""
     shim = open(os.path.join(ROOT, "hip", "cute_nt.hip")).read()
     for line in ("void split_launches(uint64_t n_tiles, int block, F&& launch) {",
-                 "const uint64_t per_launch = max_tiles_per_launch(block);",
-                 "for (uint64_t first = 0; first < n_tiles; first += per_launch) launch(first, std::min(per_launch, n_tiles - first));"):
+                 "for_each_launch(n_tiles, max_tiles_per_launch(block), [&](uint64_t first, uint64_t n, bool) { launch(first, n); });"):
         assert line in shim, line
+    loop = open(os.path.join(ROOT, "hip", "codec2_launch.hpp")).read()
+    for line in ("void for_each_launch(uint64_t total, uint64_t per_launch, F&& f) {",
+                 "for (uint64_t first = 0; first < total; first += per_launch) {",
+                 "const uint64_t n = std::min(per_launch, total - first);",
+                 "f(first, n, first + n == total);"):
+        assert line in loop, line
+    # the only loop over launches in hip/
+    sources = [f for f in os.listdir(os.path.join(ROOT, "hip")) if f.endswith((".hip", ".hpp", ".inc"))]
+    assert sum(open(os.path.join(ROOT, "hip", f)).read().count("first += per_launch") for f in sources) == 1
 
 
 def test_kmer_plan_matches_the_launcher_and_splitter_source():
