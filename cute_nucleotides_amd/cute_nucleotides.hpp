@@ -338,6 +338,26 @@ inline Hpc hpc_hip(const uint64_t* bits, size_t words, size_t len, bool with_pos
     return r;
 }
 
+/// The number of windows packed::window_counts_hip reports: (len - window) / step + 1, or 0 when len < window.
+inline size_t window_counts_n(size_t len, unsigned k, size_t window, size_t step) {
+    size_t n = 0;
+    detail::check(cnt_window_counts_n(len, k, window, step, &n));
+    return n;
+}
+
+/// Base (k = 1) or dinucleotide (k = 2) counts per window of the `len` nucleotides packed in `bits` (include/cute_nt.h "windowed
+/// composition"): window_counts_n records of 4^k counts, record j for the positions [j * step, j * step + window), entry v the k-mers
+/// wholly inside it whose value is v (k = 1: A, C, T, G; k = 2: first base + 4 * second base).  step = 0 means `window`.
+/// (C + G) / window of a k = 1 record is the window's GC content.
+inline Vec<uint32_t> window_counts_hip(const uint64_t* bits, size_t words, size_t len, unsigned k, size_t window, size_t step = 0) {
+    if (len > (words << 5)) detail::check(CNT_ELEN);
+    if (step == 0) step = window;
+    const size_t n = window_counts_n(len, k, window, step);
+    Vec<uint32_t> out(n << (2 * k));
+    detail::check(cnt_window_counts(bits, len, k, window, step, 0u, out.data(), n));
+    return out;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -424,6 +444,14 @@ inline void hpc_hip_dev(const DeviceBuffer& bits, size_t len, DeviceBuffer& out,
     const size_t most = len < out_cap ? len : out_cap;
     if (out.size_bytes() / 8 < cnt_words_for(most) || (pos && pos->size_bytes() / 8 < most)) throw std::out_of_range("hpc_hip_dev: an output is smaller than its footprint");
     detail::check(cnt_hpc_dev(bits.data(), len, 0u, out.data(), pos ? pos->data() : nullptr, out_cap, count.data(), work.data(), work.size_bytes(), nullptr));
+}
+/// Enqueue the windowed counts of `len` resident nucleotides (see packed::window_counts_hip): the packed::window_counts_n records
+/// of 4^k u32 in `out` are SET, nothing behind them is written.  No scratch.
+inline void window_counts_hip_dev(const DeviceBuffer& bits, size_t len, unsigned k, size_t window, size_t step, DeviceBuffer& out) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    const size_t n = packed::window_counts_n(len, k, window, step);
+    if (out.size_bytes() / 4 < (n << (2 * k))) throw std::out_of_range("window_counts_hip_dev: the output is smaller than its records");
+    detail::check(cnt_window_counts_dev(bits.data(), len, k, window, step, 0u, out.data(), n, nullptr));
 }
 inline void sync() { detail::check(cnt_dev_sync(nullptr)); }
 inline void set_device(int device) { detail::check(cnt_set_device(device)); }  // what DeviceBuffer allocates on

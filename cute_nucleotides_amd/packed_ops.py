@@ -2,8 +2,8 @@
 complement, reverse complement, k-mer extraction (forward and canonical), k-mer counting (the 4^k spectrum, k <= 12),
 (w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
-frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, and alphabet
-validation of ASCII buffers.  The reference does
+frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, base and dinucleotide
+counts per window (GC content on top of them), and alphabet validation of ASCII buffers.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -97,6 +97,52 @@ def kmer_counts_hip(bits, length, k, canonical=False):
     out = np.empty(bins, dtype=np.uint64)
     check(lib().cnt_kmer_counts(_p(bits), length, k, CNT_KMER_CANONICAL if canonical else 0, _p(out), out.size))
     return out
+
+
+WINDOW_COUNTS_MAX_K = 2
+
+
+def _window_shape(length, k, window, step):
+    """(n_win, step) of the windowed counts after the C rules (include/cute_nt.h "windowed composition", rule 1); step=None
+    means window"""
+    if not 1 <= k <= WINDOW_COUNTS_MAX_K:
+        raise ValueError("k must be in 1..%d" % WINDOW_COUNTS_MAX_K)
+    if step is None:
+        step = window
+    if step < 1:
+        raise ValueError("step must be at least 1")
+    if not k <= window < 2 ** 32:
+        raise ValueError("window must be in k..2^32-1")
+    if length < 0:
+        raise ValueError("length must not be negative")
+    return ((length - window) // step + 1 if length >= window else 0), step
+
+
+def window_counts_n(length, k, window, step=None):
+    """the number of windows window_counts_hip reports: (length - window) // step + 1, or 0 when length < window; there is no
+    partial window at the end"""
+    n_win, step = _window_shape(length, k, window, step)
+    out = ctypes.c_size_t(0)
+    check(lib().cnt_window_counts_n(length, k, window, step, ctypes.byref(out)))
+    assert out.value == n_win
+    return n_win
+
+
+def window_counts_hip(bits, length, k, window, step=None):
+    """Base (k = 1) or dinucleotide (k = 2) counts per window as np.uint32[n_win, 4**k] (include/cute_nt.h "windowed
+    composition"): row j counts the k-mers that lie wholly inside [j*step, j*step + window), entry v those whose kmers_hip value
+    is v (k = 1: A, C, T, G; k = 2: first base + 4 * second base).  step=None means window: adjacent windows."""
+    n_win, step = _window_shape(length, k, window, step)
+    bits = _packed(bits, length)
+    out = np.empty((n_win, 4 ** k), dtype=np.uint32)
+    check(lib().cnt_window_counts(_p(bits), length, k, window, step, 0, _p(out), n_win))
+    return out
+
+
+def gc_content_hip(bits, length, window, step=None):
+    """GC content per window as np.float64[n_win]: (C + G) / window, from window_counts_hip with k = 1"""
+    c = window_counts_hip(bits, length, 1, window, step)
+    return (c[:, 1].astype(np.float64) + c[:, 3]) / window
 
 
 def _n_windows(length, k, w):
@@ -462,6 +508,22 @@ def kmer_counts_dev(bits, length, k, canonical=False, out=None):
     _enqueue(bits, lib().cnt_kmer_counts_dev, ctypes.c_void_p(bits.data_ptr()), length, k, CNT_KMER_CANONICAL if canonical else 0,
              ctypes.c_void_p(out.data_ptr()), out.numel())
     return out[:bins]
+
+
+def window_counts_dev(bits, length, k, window, step=None, out=None):
+    """Device tier of window_counts_hip, enqueued on torch's current stream: returns the (n_win, 4**k) view of an int32 CUDA
+    tensor (the bit pattern of the u32 counts).  A given `out` (contiguous int32, on the input's device, >= n_win * 4**k
+    entries, at an 8-byte aligned address) is SET in those entries and left alone behind them."""
+    n_win, step = _window_shape(length, k, window, step)
+    torch = _packed_dev(bits, length)
+    bins = 4 ** k
+    if out is None:
+        out = torch.empty(n_win * bins, dtype=torch.int32, device=bits.device)
+    elif out.dtype != torch.int32 or not out.is_cuda or not out.is_contiguous() or out.device != bits.device or out.numel() < n_win * bins:
+        raise ValueError("out must be a contiguous int32 CUDA tensor on the input's device with >= %d elements" % (n_win * bins))
+    _enqueue(bits, lib().cnt_window_counts_dev, ctypes.c_void_p(bits.data_ptr()), length, k, window, step, 0, ctypes.c_void_p(out.data_ptr()),
+             out.numel() // bins)
+    return out.reshape(-1)[: n_win * bins].view(n_win, bins)
 
 
 def _work_bytes(fn, *args):

@@ -25,6 +25,7 @@
 //   translate_abi.inc   codon translation, any frame, either strand
 //   orf_abi.inc         open-reading-frame scan, one strand or both
 //   hpc_abi.inc         homopolymer compression, with run positions
+//   window_count_abi.inc  windowed base and dinucleotide counts
 // counted_output.hpp (under the minimizers, pattern search and the ORF scan) holds the host helpers of the calls whose output
 // size depends on the data, on top of host_call.
 #include "../include/cute_nt.h"
@@ -169,7 +170,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc, window_count_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -900,3 +901,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "translate_abi.inc"
 #include "orf_abi.inc"
 #include "hpc_abi.inc"
+#include "window_count_abi.inc"

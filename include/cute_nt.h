@@ -719,6 +719,48 @@ int cnt_checksum_words_dev(const void *d_words, size_t first_word, size_t words,
 /* *d_count (device u64, caller zeroes it) += number of differing bytes. */
 int cnt_count_mismatch_dev(const void *d_a, const void *d_b, size_t nbytes, void *d_count, void *stream);
 
+/* ---- windowed composition on packed sequences ---------------------------------- */
+/* Base (k = 1) and dinucleotide (k = 2) counts per window along a packed sequence, 1 <= k <= CNT_WINDOW_COUNTS_MAX_K = 2: what GC
+ * content, GC skew (G-C)/(G+C), CpG observed/expected and AT-rich screening are made of, without decoding.  Layout, `len` and the
+ * two tiers are those of the packed-domain operations above, and the SHARED MEMORY rules of that section apply to this block:
+ * `out` is written, its extent is the n_win records, and it shares no byte with the cnt_words_for(len) input words.
+ * With a window length `window` and a step `step`, both in nucleotides:
+ *   n_win = len >= window ? (len - window) / step + 1 : 0          (no partial window at the end)
+ *   window j covers the positions [j*step, j*step + window)
+ *   x_p   = the value cnt_kmers writes for k-mer p with flags 0 (k = 2: code(p) | code(p+1) << 2)
+ *   out[j * 4^k + v] = #{ p : j*step <= p and p + k <= j*step + window and x_p == v },  v in [0, 4^k)
+ * Records are 4^k uint32_t, record-major, in code order A0 C1 T2 G3.  A k-mer that straddles a window's end is not counted: a
+ * k = 2 record sums to window - 1.  Every entry of the records 0 .. n_win is SET exactly once -- the caller zeroes nothing, unlike
+ * cnt_kmer_counts_dev -- and nothing past record n_win is written.  Input bits beyond len are ignored (k = 2: the position behind
+ * the last window's last base may be tail garbage of the last word; it is never part of a counted k-mer).
+ * Counts are u32 and not the u64 of the whole-sequence table: window < 2^32 is enforced, so no count can wrap, and u32 halves the
+ * write stream, which dominates at small windows.
+ * cnt_window_counts_n: *n_windows = n_win.
+ * Errors, all before any device work, in this order:
+ *   1. k == 0, k > 2, flags != 0, step == 0, window < k or window >= 2^32: CNT_EINVAL; the query: also a NULL n_windows.
+ *   2. n_win == 0: CNT_OK; nothing is touched in either tier, whatever the pointers are.
+ *   3. a NULL or not 8-B aligned bits or out: CNT_EINVAL.
+ *   4. out_cap (records) < n_win: CNT_ECAP; nothing is written.
+ *   5. the n_win * 4^k * 4 bytes of out overlapping the cnt_words_for(len) input words: CNT_EINVAL (rule 1 of the packed-domain
+ *      section: buffers that touch are fine, a refused call writes nothing).
+ * Device tier: enqueue-only on the caller's stream: no allocation, no synchronisation, no scratch, capturable in a graph; d_bits
+ *   at any 8-B phase; no word outside the cnt_words_for(len) input words is read and nothing outside the n_win records written.
+ *   Parallelism follows the window length.  Up to 8192 nt a group of 1..64 lanes (an eighth of the words a window can span, rounded
+ *   up to a power of two) owns a window, sums over the group by shuffles and stores the record once: one launch.  A longer window is cut
+ *   into 8192-nt pieces; workgroups count runs of pieces and add into the record with 32-bit atomics, behind a kernel of the same
+ *   call that zeroes the records: two launches, and window == len is spread over the whole chip.
+ *   Measured on one MI355X, 2026-10-20, product build, 2^30 nt of random ACGT (DESIGN.md 4 "Windowed counts",
+ *   profiles/window_counts_bench.jsonl), k = 1 / k = 2: window = step = 64 takes 0.102 / 0.340 ms, 1024: 0.072 / 0.151 ms, 65536:
+ *   0.068 / 0.143 ms, window = len: 0.076 / 0.142 ms (0.34 x / 0.66 x cnt_kmer_counts_dev at the same k in the same run);
+ *   window = 1000 with step = 100 takes 0.646 / 1.689 ms: overlapping windows recount their words, window / step times the input.
+ * Host tier: synchronous; pinned bits and out are used in place, otherwise both are staged. */
+#define CNT_WINDOW_COUNTS_MAX_K 2
+int cnt_window_counts_n(size_t len, unsigned k, size_t window, size_t step, size_t *n_windows);
+int cnt_window_counts_dev(const void *d_bits, size_t len, unsigned k, size_t window, size_t step, unsigned flags,
+                          void *d_out, size_t out_cap, void *stream);
+int cnt_window_counts(const uint64_t *bits, size_t len, unsigned k, size_t window, size_t step, unsigned flags,
+                      uint32_t *out, size_t out_cap);
+
 /* Kernel selection for A/B runs: LAB BUILD ONLY.  The product library (libcute_nt_hip.so) holds the shipped default of every
  * kernel family plus the any-alignment kernels and has NO run-time selection of code: cnt_set_tuning answers CNT_EINVAL for
  * every key, the getters answer constants ("encode" = 0, "encode_variants" = 1, "small_nt" = 2^17, "lab_build" = 0, ...) --

@@ -86,6 +86,9 @@ extern "C" {
     fn cnt_hpc_work_bytes(len: usize, bytes: *mut usize) -> c_int;
     fn cnt_hpc_dev(d_bits: *const c_void, len: usize, flags: c_uint, d_out: *mut c_void, d_pos: *mut c_void, out_cap: usize, d_count: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_hpc(bits: *const u64, len: usize, flags: c_uint, out: *mut u64, pos: *mut u64, out_cap: usize, count: *mut u64) -> c_int;
+    fn cnt_window_counts_n(len: usize, k: c_uint, window: usize, step: usize, n_windows: *mut usize) -> c_int;
+    fn cnt_window_counts_dev(d_bits: *const c_void, len: usize, k: c_uint, window: usize, step: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
+    fn cnt_window_counts(bits: *const u64, len: usize, k: c_uint, window: usize, step: usize, flags: c_uint, out: *mut u32, out_cap: usize) -> c_int;
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -742,6 +745,28 @@ pub fn hpc_hip(bits: &[u64], len: usize) -> (Vec<u64>, usize, Vec<u64>) {
     (out, n as usize, pos)
 }
 
+/// The number of windows `window_counts_hip` reports: `(len - window) / step + 1`, or 0 when `len < window` (no partial window).
+pub fn window_counts_n(len: usize, k: u32, window: usize, step: usize) -> usize {
+    let mut n: usize = 0;
+    unsafe { check(cnt_window_counts_n(len, k, window, step, &mut n)) };
+    n
+}
+
+/// Base (`k = 1`) or dinucleotide (`k = 2`) counts per window: `window_counts_n` records of `4^k` counts, record `j` for the
+/// positions `[j * step, j * step + window)`, entry `v` the k-mers wholly inside it whose `kmers_hip` value is `v` (`k = 1`:
+/// A, C, T, G; `k = 2`: first base + 4 * second base).  `(C + G) / window` of a `k = 1` record is the window's GC content.
+pub fn window_counts_hip(bits: &[u64], len: usize, k: u32, window: usize, step: usize) -> Vec<u32> {
+    need(bits, len);
+    let n = window_counts_n(len, k, window, step);
+    let entries = n << (2 * k);
+    let mut res: Vec<u32> = Vec::with_capacity(entries);
+    unsafe {
+        check(cnt_window_counts(bits.as_ptr(), len, k, window, step, 0, res.as_mut_ptr(), n));
+        res.set_len(entries);
+    }
+    res
+}
+
 /// Number of bytes outside `ACGTUacgtu` (with `allow_n` also `N`/`n` are legal); 0 = a valid sequence.
 pub fn validate_hip(n: &[u8], allow_n: bool) -> u64 {
     let mut bad: u64 = 0;
@@ -1004,6 +1029,19 @@ pub fn hpc_hip_dev(d_bits: &DeviceBuffer, len: usize, d_out: &DeviceBuffer, d_po
         None => std::ptr::null_mut(),
     };
     unsafe { check(cnt_hpc_dev(d_bits.ptr, len, 0, d_out.ptr, pos_ptr, out_cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Enqueue the windowed counts of `len` device-resident nucleotides (see `window_counts_hip`): the `window_counts_n` records of
+/// `4^k` u32 in `d_out` are SET, nothing behind them is written.  No scratch.
+pub fn window_counts_hip_dev(d_bits: &DeviceBuffer, len: usize, k: u32, window: usize, step: usize, d_out: &DeviceBuffer) {
+    if len > (d_bits.bytes / 8) << 5 {
+        panic!("The length is greater than the number of nucleotides!");
+    }
+    let n = window_counts_n(len, k, window, step);
+    if d_out.bytes / 4 < n << (2 * k) {
+        panic!("the output is smaller than its records");
+    }
+    unsafe { check(cnt_window_counts_dev(d_bits.ptr, len, k, window, step, 0, d_out.ptr, n, std::ptr::null_mut())) };
 }
 
 /// Make `device` the calling thread's current device (what `DeviceBuffer::new` allocates on).
