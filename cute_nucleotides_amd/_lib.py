@@ -141,6 +141,9 @@ SIGNATURES = {
     "cnt_window_counts_n": (_int, [_sz, _uint, _sz, _sz, ctypes.POINTER(_sz)]),
     "cnt_window_counts_dev": (_int, [_vp, _sz, _uint, _sz, _sz, _uint, _vp, _sz, _vp]),
     "cnt_window_counts": (_int, [_vp, _sz, _uint, _sz, _sz, _uint, _vp, _sz]),
+    "cnt_fasta_to_bits_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
+    "cnt_fasta_to_bits_dev": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_fasta_to_bits": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _vp, _sz, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

@@ -358,6 +358,45 @@ inline Vec<uint32_t> window_counts_hip(const uint64_t* bits, size_t words, size_
     return out;
 }
 
+/// What packed::fasta_to_bits_hip returns: the n kept nucleotides packed like any sequence in `out`, one entry per header line
+/// in `rec_text` (the byte offset of its '>') and `rec_start` (the position in `out` of the record's first base; record r ends
+/// where record r + 1 starts, the last one at n), and the number of kept bytes outside the alphabet.
+struct Fasta {
+    Vec<uint64_t> out;
+    size_t n = 0;
+    Vec<uint64_t> rec_text, rec_start;
+    uint64_t invalid = 0;
+};
+
+/// Encode FASTA text (include/cute_nt.h "text formats: FASTA"): header lines, line feeds and carriage returns are dropped, every
+/// other byte is encoded as n_to_bits_hip encodes it (`strict_lut`: BYTE_LUT), `allow_n` takes N / n out of the invalid count.
+/// The record arrays start at a guess and are sized to the reported number of header lines once if the guess was short.
+inline Fasta fasta_to_bits_hip(const uint8_t* text, size_t text_len, bool strict_lut = false, bool allow_n = false) {
+    const unsigned flags = (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u);
+    size_t rec_cap = text_len < 1024 ? text_len : text_len / 4096 + 1024;
+    Fasta r;
+    uint64_t counts[3] = {0, 0, 0};
+    r.out.resize(cnt_words_for(text_len));
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        r.rec_text.resize(rec_cap);
+        r.rec_start.resize(rec_cap);
+        const int rc = cnt_fasta_to_bits(text, text_len, flags, r.out.data(), text_len, rec_cap ? r.rec_text.data() : nullptr,
+                                         rec_cap ? r.rec_start.data() : nullptr, rec_cap, counts);
+        if (rc == CNT_ECAP && attempt == 0) {
+            rec_cap = counts[CNT_FASTA_RECORDS];
+            continue;
+        }
+        detail::check(rc);
+        break;
+    }
+    r.n = counts[CNT_FASTA_N];
+    r.invalid = counts[CNT_FASTA_INVALID];
+    r.out.resize(cnt_words_for(r.n));
+    r.rec_text.resize(counts[CNT_FASTA_RECORDS]);
+    r.rec_start.resize(counts[CNT_FASTA_RECORDS]);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -444,6 +483,25 @@ inline void hpc_hip_dev(const DeviceBuffer& bits, size_t len, DeviceBuffer& out,
     const size_t most = len < out_cap ? len : out_cap;
     if (out.size_bytes() / 8 < cnt_words_for(most) || (pos && pos->size_bytes() / 8 < most)) throw std::out_of_range("hpc_hip_dev: an output is smaller than its footprint");
     detail::check(cnt_hpc_dev(bits.data(), len, 0u, out.data(), pos ? pos->data() : nullptr, out_cap, count.data(), work.data(), work.size_bytes(), nullptr));
+}
+inline size_t fasta_to_bits_work_bytes(size_t text_len) {
+    size_t bytes = 0;
+    detail::check(cnt_fasta_to_bits_work_bytes(text_len, &bytes));
+    return bytes;
+}
+/// Enqueue the FASTA encode of `text_len` resident bytes (see packed::fasta_to_bits_hip): `counts` (three u64) is SET to n, the
+/// number of header lines and the invalid count; `out` receives the first min(n, out_cap) nucleotides and holds at least
+/// cnt_words_for(min(text_len, out_cap)) words; `rec_text` and `rec_start` (both or neither) hold at least min(text_len, rec_cap)
+/// entries; `work` >= fasta_to_bits_work_bytes(text_len) bytes of any contents.
+inline void fasta_to_bits_hip_dev(const DeviceBuffer& text, size_t text_len, DeviceBuffer& out, size_t out_cap, DeviceBuffer* rec_text, DeviceBuffer* rec_start,
+                                  size_t rec_cap, DeviceBuffer& counts, DeviceBuffer& work, bool strict_lut = false, bool allow_n = false) {
+    if (text_len > text.size_bytes() || counts.size_bytes() < 24) throw std::out_of_range("fasta_to_bits_hip_dev: sizes");
+    const size_t most = text_len < out_cap ? text_len : out_cap, rmost = text_len < rec_cap ? text_len : rec_cap;
+    if (out.size_bytes() / 8 < cnt_words_for(most) || (rec_text && rec_text->size_bytes() / 8 < rmost) || (rec_start && rec_start->size_bytes() / 8 < rmost))
+        throw std::out_of_range("fasta_to_bits_hip_dev: an output is smaller than its footprint");
+    detail::check(cnt_fasta_to_bits_dev(text.data(), text_len, (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u), out.data(), out_cap,
+                                        rec_text ? rec_text->data() : nullptr, rec_start ? rec_start->data() : nullptr, rec_cap, counts.data(), work.data(),
+                                        work.size_bytes(), nullptr));
 }
 /// Enqueue the windowed counts of `len` resident nucleotides (see packed::window_counts_hip): the packed::window_counts_n records
 /// of 4^k u32 in `out` are SET, nothing behind them is written.  No scratch.

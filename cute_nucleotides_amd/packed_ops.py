@@ -3,7 +3,8 @@ complement, reverse complement, k-mer extraction (forward and canonical), k-mer 
 (w,k)-minimizers, approximate pattern search on one or both strands, region extraction (a subsequence at any start, or many
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
 frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, base and dinucleotide
-counts per window (GC content on top of them), and alphabet validation of ASCII buffers.  The reference does
+counts per window (GC content on top of them), alphabet validation of ASCII buffers, and the encode of FASTA text with its
+record table.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -443,6 +444,62 @@ def hpc_minimizers_hip(bits, length, k, w, flags=0):
     return run_pos[pos.astype(np.int64)], val
 
 
+def _fasta_text(text):
+    """the host tier's text: bytes, bytearray, mmap, memoryview or a uint8 array, as a contiguous uint8 array without a copy"""
+    if isinstance(text, np.ndarray):
+        return _u8(text)
+    try:
+        return np.frombuffer(text, dtype=np.uint8)
+    except (TypeError, ValueError, BufferError):
+        raise TypeError("text must be bytes, a bytearray, an mmap or a uint8 array")
+
+
+def fasta_to_bits_hip(text, strict_lut=False, allow_n=False):
+    """Encode FASTA text (include/cute_nt.h "text formats: FASTA"): header lines, line feeds and carriage returns are dropped, every
+    other byte is encoded as n_to_bits_hip encodes it (strict_lut: BYTE_LUT).  `text` is bytes, a bytearray, an mmap or a uint8
+    array.  Returns (words, n, rec_text, rec_start, invalid): np.uint64[words_for(n)] holding the n kept nucleotides, so that every
+    call here takes (words, n); per header line the byte offset of its '>' and the position in `words` of the record's first base
+    (record r ends at rec_start[r + 1], the last one at n; fasta_names gives the names); and the number of kept bytes outside
+    ACGTUacgtu (allow_n: and Nn).  The record arrays start at a guess of the number of header lines and are sized to the reported
+    number once if the guess was short."""
+    text = _fasta_text(text)
+    length = text.size
+    flags = (_lib.CNT_STRICT_LUT if strict_lut else 0) | (CNT_ALLOW_N if allow_n else 0)
+    out = np.empty(lib().cnt_words_for(length), dtype=np.uint64)
+    rec_cap = min(length, length // 4096 + 1024)  # a header every 4096 bytes or so
+    counts = (ctypes.c_uint64 * 3)()
+    for attempt in range(2):
+        rec_text = np.empty(rec_cap, dtype=np.uint64)
+        rec_start = np.empty(rec_cap, dtype=np.uint64)
+        rc = lib().cnt_fasta_to_bits(_p(text), length, flags, _p(out) if length else None, length, _p(rec_text), _p(rec_start), rec_cap, counts)
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            rec_cap = counts[1]
+            continue
+        check(rc)
+        n, records = counts[0], counts[1]
+        return out[: lib().cnt_words_for(n)], n, rec_text[:records], rec_start[:records], counts[2]
+
+
+def fasta_names(text, rec_text):
+    """the header lines of a FASTA text at the byte offsets fasta_to_bits_hip reported, as a list of bytes: each without its '>'
+    and without its line end (a line feed, or a carriage return and a line feed; the last line may have neither)"""
+    buf = _fasta_text(text)
+    names = []
+    for at in np.asarray(rec_text, dtype=np.uint64).tolist():
+        if at >= buf.size or buf[at] != 0x3E:
+            raise ValueError("no header line starts at byte %d" % at)
+        line, look = b"", 256
+        while True:  # a look at a time, so that a short name in a long text costs its own length
+            piece = buf[at + 1 + len(line) : at + 1 + len(line) + look].tobytes()
+            end = piece.find(b"\n")
+            line += piece if end < 0 else piece[:end]
+            if end >= 0 or len(piece) < look:
+                break
+            look *= 4
+        names.append(line[:-1] if line.endswith(b"\r") else line)
+    return names
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -727,6 +784,53 @@ def hpc_dev(bits, length, out, count, work, pos=None, out_cap=None):
     _enqueue(bits, lib().cnt_hpc_dev, ctypes.c_void_p(bits.data_ptr()), length, 0, ctypes.c_void_p(out.data_ptr() or count.data_ptr()),
              ctypes.c_void_p(pos.data_ptr() or count.data_ptr()) if pos is not None else None, out_cap, ctypes.c_void_p(count.data_ptr()),
              ctypes.c_void_p(work.data_ptr() or count.data_ptr()), work.numel() * work.element_size())
+
+
+def fasta_to_bits_work_bytes(text_len):
+    """bytes of device scratch cnt_fasta_to_bits_dev needs for a text of this many bytes (0 without a byte)"""
+    return _work_bytes(lib().cnt_fasta_to_bits_work_bytes, text_len)
+
+
+def fasta_to_bits_dev(text, out, counts, work, rec_text=None, rec_start=None, out_cap=None, rec_cap=None, strict_lut=False, allow_n=False):
+    """Device tier of fasta_to_bits_hip, enqueued on torch's current stream without a synchronisation; returns nothing.  All
+    tensors are the caller's, contiguous and on the text's device: `text` (uint8, at any byte address) the FASTA bytes, `out`
+    (int64) receives the kept nucleotides packed, `rec_text` and `rec_start` (int64, both or neither) the record table, `counts`
+    (int64, three elements) is SET to n, the number of header lines and the invalid count, `work` holds >=
+    fasta_to_bits_work_bytes(text.numel()) bytes of any contents.  `out_cap` (nucleotides) and `rec_cap` (records) default to what
+    the outputs can hold and bound what is written.  Every tensor may be reused across calls, e.g. in a captured graph."""
+    torch = _dev_guard(text)
+    if text.dtype != torch.uint8:
+        raise TypeError("text must be a uint8 tensor")
+    if (rec_text is None) != (rec_start is None):
+        raise ValueError("rec_text and rec_start go together")
+    for name, t, dtype in (("out", out, torch.int64), ("rec_text", rec_text, torch.int64), ("rec_start", rec_start, torch.int64),
+                           ("counts", counts, torch.int64), ("work", work, None)):
+        if t is None and name.startswith("rec_"):
+            continue
+        if not hasattr(t, "is_cuda") or (dtype is not None and t.dtype != dtype):
+            raise TypeError("%s must be a%s tensor" % (name, "n int64" if dtype is not None else ""))
+        if not t.is_cuda or not t.is_contiguous() or t.device != text.device:
+            raise ValueError("%s must be a contiguous CUDA tensor on the text's device" % name)
+    if counts.numel() < 3:
+        raise ValueError("counts must hold three elements")
+    length = text.numel()
+    need = fasta_to_bits_work_bytes(length)
+    if work.numel() * work.element_size() < need:
+        raise ValueError("work must hold >= %d bytes" % need)
+    fits = min(length, out.numel() * 32)
+    out_cap = fits if out_cap is None else int(out_cap)
+    if out_cap < 0 or min(length, out_cap) > fits:
+        raise ValueError("out_cap nucleotides do not fit out")
+    rec_fits = min(length, rec_text.numel(), rec_start.numel()) if rec_text is not None else 0
+    rec_cap = rec_fits if rec_cap is None else int(rec_cap)
+    if rec_cap < 0 or (rec_text is not None and min(length, rec_cap) > rec_fits):
+        raise ValueError("rec_cap records do not fit the record arrays")
+    spare = counts.data_ptr()  # an empty tensor has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    flags = (_lib.CNT_STRICT_LUT if strict_lut else 0) | (CNT_ALLOW_N if allow_n else 0)
+    _enqueue(text, lib().cnt_fasta_to_bits_dev, ctypes.c_void_p(text.data_ptr()), length, flags, ctypes.c_void_p(out.data_ptr() or spare), out_cap,
+             ctypes.c_void_p(rec_text.data_ptr() or spare) if rec_text is not None else None,
+             ctypes.c_void_p(rec_start.data_ptr() or spare) if rec_text is not None else None, rec_cap, ctypes.c_void_p(counts.data_ptr()),
+             ctypes.c_void_p(work.data_ptr() or spare), work.numel() * work.element_size())
 
 
 def validate_dev(n, allow_n=False, acc=None):

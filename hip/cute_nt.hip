@@ -170,7 +170,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc, window_count_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc, window_count_abi.inc, fasta_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -190,8 +190,9 @@ struct HostBuf {
 // With a `result`, aux's first word ends in *result, and starts from 0 when `zero` (a count the call adds to).  Every exit after
 // the first enqueue goes through finish(): no copy can still read or write the caller's pageable memory after the return (the
 // retire() rule of host_tier.inc).
+// The long form brings back `result_words` words of aux, and result[sizing] is the one that sizes the `counted` buffers.
 template <size_t N, typename F>
-int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool zero, F&& dev) {
+int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, size_t result_words, size_t sizing, bool zero, F&& dev) {
     DevCtx* c = nullptr;
     CNT_TRY(t_ctx.get(&c));
     CNT_TRY(c->ensure_streams());
@@ -235,12 +236,12 @@ int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool ze
     for (size_t i = 0; i < N; ++i)
         if (staged && b[i].p && b[i].dir == Dir::out && rc == CNT_OK)
             rc = hip_rc(hipMemcpyAsync(h[i], d[i], b[i].bytes, hipMemcpyDeviceToHost, s));
-    if (rc == CNT_OK && result) rc = hip_rc(hipMemcpyAsync(result, c->d_aux[2], 8, hipMemcpyDeviceToHost, s));
+    if (rc == CNT_OK && result) rc = hip_rc(hipMemcpyAsync(result, c->d_aux[2], 8 * result_words, hipMemcpyDeviceToHost, s));
     CNT_TRY(finish(s, rc));
     size_t got[N] = {};  // the `counted` outputs, now that *result is known
     bool copying = false;
     for (size_t i = 0; i < N; ++i) {
-        got[i] = staged && b[i].p && b[i].dir == Dir::counted ? std::min<uint64_t>(*result, b[i].bytes / 8) * 8 : 0;
+        got[i] = staged && b[i].p && b[i].dir == Dir::counted ? std::min<uint64_t>(result[sizing], b[i].bytes / 8) * 8 : 0;
         if (got[i] && rc == CNT_OK) rc = hip_rc(hipMemcpyAsync(h[i], d[i], got[i], hipMemcpyDeviceToHost, s));
         copying = copying || got[i];
     }
@@ -248,6 +249,10 @@ int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool ze
     for (size_t i = 0; i < N; ++i)
         if (!bounce[i].empty() && b[i].dir != Dir::in) memcpy(const_cast<void*>(b[i].p), bounce[i].data(), b[i].dir == Dir::out ? b[i].bytes : got[i]);
     return CNT_OK;
+}
+template <size_t N, typename F>
+int host_call(const HostBuf (&b)[N], size_t aux_bytes, uint64_t* result, bool zero, F&& dev) {
+    return host_call(b, aux_bytes, result, 1, 0, zero, static_cast<F&&>(dev));
 }
 
 }  // namespace
@@ -902,3 +907,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "orf_abi.inc"
 #include "hpc_abi.inc"
 #include "window_count_abi.inc"
+#include "fasta_abi.inc"

@@ -761,6 +761,70 @@ int cnt_window_counts_dev(const void *d_bits, size_t len, unsigned k, size_t win
 int cnt_window_counts(const uint64_t *bits, size_t len, unsigned k, size_t window, size_t step, unsigned flags,
                       uint32_t *out, size_t out_cap);
 
+/* ---- text formats: FASTA ---------------------------------------------------------- */
+/* FASTA text straight to packed words, with a record table: what "a FASTA file fed in with its line feeds" needs instead of a
+ * strip on the CPU in front of the encoder.  For the bytes t_0 .. t_{L-1} of `text`, L = text_len, and nothing outside them:
+ *   line start    p is one iff p == 0 or t_{p-1} == 0x0A; the byte in front of `text` is never looked at
+ *   header byte   t_p is one iff the last line start <= p holds '>' (0x3E); a '>' anywhere else is an ordinary byte, and a
+ *                 header at the end of the text needs no line feed
+ *   dropped       every header byte, every 0x0A, every 0x0D; every other byte is KEPT (spaces, digits, N, bytes >= 0x80), at
+ *                 the positions q_0 < .. < q_{n-1}
+ *   out           exactly what cnt_n_to_bits_ex(kept bytes, n, out, ., flags & CNT_STRICT_LUT) writes: (byte>>1)&3 by default,
+ *                 BYTE_LUT with CNT_STRICT_LUT, the encoder's layout, the unused bits of the last word zero.  out_cap is in
+ *                 NUCLEOTIDES: with m = min(n, out_cap) the words [0, cnt_words_for(m)) are written and the code slots at or
+ *                 past m in the last one are 0.  The footprint rule is cnt_hpc's with text_len for len:
+ *                 cnt_words_for(min(text_len, out_cap)) words, unspecified contents behind the result, nothing outside touched
+ *   records       the line starts that hold '>' are h_0 < .. < h_{R-1}: rec_text[r] = h_r, the byte offset of the '>', and
+ *                 rec_start[r] = #{ j : q_j < h_r }, the position in `out` of the record's first base.  Record r is
+ *                 [rec_start[r], rec_start[r+1]), the last one ends at n; bases in front of the first header belong to no
+ *                 record, an empty record is legal.  Entries r < min(R, rec_cap) are written and nothing past them.  Both
+ *                 arrays may be NULL together, whatever rec_cap is
+ *   counts        three u64 the call SETS, as cnt_hpc's count is set, whether or not the results fitted:
+ *                 counts[CNT_FASTA_N] = n, counts[CNT_FASTA_RECORDS] = R, counts[CNT_FASTA_INVALID] = the number of kept bytes
+ *                 that cnt_validate with flags & CNT_ALLOW_N counts
+ *   flags         any of CNT_STRICT_LUT | CNT_ALLOW_N; every other bit is refused, CNT_TAIL_LUT included
+ * Checks, all before any device work, in this order:
+ *   1. an unknown flag, or, for the query, a NULL bytes: CNT_EINVAL.
+ *   2. text_len == 0: CNT_OK, counts set to zeros when it is given, nothing else touched.
+ *   3. a NULL text, out or counts: CNT_EINVAL.
+ *   4. an out, counts, rec_text or rec_start that is not 8-B aligned: CNT_EINVAL.  text may be at ANY byte address.
+ *   5. one record array without the other: CNT_EINVAL.
+ *   6. a written buffer sharing a byte with another buffer of the call (rule 1 of the packed-domain section: buffers that touch
+ *      are fine, a refused call writes nothing): CNT_EINVAL.  The extents are text_len bytes, the footprint of out,
+ *      min(text_len, rec_cap) entries of each record array and 24 bytes of counts.
+ *   7. device tier: a NULL d_work, work_bytes below the query's answer, or the query's bytes of d_work overlapping anything
+ *      else: CNT_EINVAL.
+ * text_len goes up to 2^36.
+ * Device tier: enqueue-only on the caller's stream: no allocation, no synchronisation, capturable in a graph; d_work is caller
+ *   scratch that nobody needs zeroed.  No byte outside [d_text, d_text + text_len) is read; nothing outside the footprint, the
+ *   clipped record arrays and the counts is written.  Four passes over tiles of 8192 bytes, 256 lanes of 32 bytes (hip/
+ *   fasta_kernels.hpp): a summary pass (per tile: the kind of its last line start, its kept and invalid bytes, its header lines);
+ *   ONE workgroup that carries "inside a header" from tile to tile -- through tiles without any line start -- and scans the
+ *   counts (no atomic: a dirty text costs what a clean one costs, unlike the one counter of cnt_n_to_bits_checked_dev);
+ *   cnt_hpc's edge zeroing; and a write pass that encodes a lane's 32 bytes, compresses them to the kept codes, assembles the
+ *   tile's words in LDS and stores them coalesced -- the at most two words a tile shares with others by cnt_hpc's 64-bit
+ *   compare-and-swap, the one merge a pinned buffer behind a PCIe link supports.
+ *   Measured on one MI355X, 2026-10-20, product build (DESIGN.md 4 "FASTA encode", profiles/fasta_bench.jsonl): 2^30 bytes of 60-column
+ *   FASTA with a 40-byte header every 2^20 bases take 1.040 ms with line feeds and 1.040 ms with carriage return + line feed
+ *   (1032 GB/s of text).  In the same run cnt_n_to_bits_checked_dev on the already-stripped bytes takes 0.199 / 0.198 ms (the call costs
+ *   5.215 x / 5.247 x that floor), a torch boolean-mask strip of the text followed by cnt_n_to_bits_dev 9.568 / 9.387 ms with the mask
+ *   given (9.2 x / 9.0 x the call) and 3478 / 3432 ms with the mask built in torch first, and bytes.translate plus a header filter on
+ *   the CPU followed by the host-tier encode 3.1 / 2.9 s.  rocprofv3 --kernel-trace --stats (profiles/fasta_kernel_trace.md) splits
+ *   a call into fasta_summary 342 us, fasta_scan 131 us, hpc_zero_edges 7 us, fasta_write_rec 572 us.  The two tile passes are not bound by
+ *   memory: a lane spends about 50 VALU operations per dword on its byte masks; no counters were collected.
+ * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
+ *   n > out_cap or R > rec_cap the clipped results are written and the call returns CNT_ECAP after the work, as cnt_hpc does.
+ * Out of scope: FASTQ, multi-line ';' comments, a 5-letter variant, a nucleotide-to-byte-offset map, line-wrapped decode, gzip. */
+#define CNT_FASTA_N 0        /* counts[0]: nucleotides kept            */
+#define CNT_FASTA_RECORDS 1  /* counts[1]: header lines                */
+#define CNT_FASTA_INVALID 2  /* counts[2]: kept bytes cnt_validate would count */
+int cnt_fasta_to_bits_work_bytes(size_t text_len, size_t *bytes);
+int cnt_fasta_to_bits_dev(const void *d_text, size_t text_len, unsigned flags, void *d_out, size_t out_cap,
+                          void *d_rec_text, void *d_rec_start, size_t rec_cap, void *d_counts, void *d_work,
+                          size_t work_bytes, void *stream);
+int cnt_fasta_to_bits(const uint8_t *text, size_t text_len, unsigned flags, uint64_t *out, size_t out_cap,
+                      uint64_t *rec_text, uint64_t *rec_start, size_t rec_cap, uint64_t counts[3]);
+
 /* Kernel selection for A/B runs: LAB BUILD ONLY.  The product library (libcute_nt_hip.so) holds the shipped default of every
  * kernel family plus the any-alignment kernels and has NO run-time selection of code: cnt_set_tuning answers CNT_EINVAL for
  * every key, the getters answer constants ("encode" = 0, "encode_variants" = 1, "small_nt" = 2^17, "lab_build" = 0, ...) --

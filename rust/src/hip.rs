@@ -89,6 +89,9 @@ extern "C" {
     fn cnt_window_counts_n(len: usize, k: c_uint, window: usize, step: usize, n_windows: *mut usize) -> c_int;
     fn cnt_window_counts_dev(d_bits: *const c_void, len: usize, k: c_uint, window: usize, step: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, stream: *mut c_void) -> c_int;
     fn cnt_window_counts(bits: *const u64, len: usize, k: c_uint, window: usize, step: usize, flags: c_uint, out: *mut u32, out_cap: usize) -> c_int;
+    fn cnt_fasta_to_bits_work_bytes(text_len: usize, bytes: *mut usize) -> c_int;
+    fn cnt_fasta_to_bits_dev(d_text: *const c_void, text_len: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, d_rec_text: *mut c_void, d_rec_start: *mut c_void, rec_cap: usize, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_fasta_to_bits(text: *const u8, text_len: usize, flags: c_uint, out: *mut u64, out_cap: usize, rec_text: *mut u64, rec_start: *mut u64, rec_cap: usize, counts: &mut [u64; 3]) -> c_int; // uint64_t counts[3]: a reference to three u64 is that pointer
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -745,6 +748,38 @@ pub fn hpc_hip(bits: &[u64], len: usize) -> (Vec<u64>, usize, Vec<u64>) {
     (out, n as usize, pos)
 }
 
+/// FASTA text to packed words as `(out, n, rec_text, rec_start, invalid)`: header lines, line feeds and carriage returns are
+/// dropped and every other byte is encoded as `n_to_bits_hip` encodes it (`strict_lut`: the byte table).  `rec_text[r]` is the
+/// byte offset of header line `r`, `rec_start[r]` the position in `out` of its first base; record `r` ends where record `r + 1`
+/// starts, the last one at `n`.  `invalid` counts the kept bytes outside `ACGTUacgtu` (`allow_n`: and `Nn`).
+pub fn fasta_to_bits_hip(text: &[u8], strict_lut: bool, allow_n: bool) -> (Vec<u64>, usize, Vec<u64>, Vec<u64>, u64) {
+    let len = text.len();
+    let flags: c_uint = (if strict_lut { 1 } else { 0 }) | (if allow_n { 2 } else { 0 });
+    let mut out: Vec<u64> = vec![0u64; words_for(len)];
+    if len == 0 {
+        return (out, 0, Vec::new(), Vec::new(), 0);
+    }
+    // a header every 4096 bytes or so; a longer table is fetched again at its reported size
+    let mut rec_cap = std::cmp::min(len, len / 4096 + 1024);
+    let mut rec_text: Vec<u64> = Vec::with_capacity(rec_cap);
+    let mut rec_start: Vec<u64> = Vec::with_capacity(rec_cap);
+    let mut counts = [0u64; 3];
+    unsafe {
+        let fits = cnt_fasta_to_bits(text.as_ptr(), len, flags, out.as_mut_ptr(), len, rec_text.as_mut_ptr(), rec_start.as_mut_ptr(), rec_cap, &mut counts) == 0;
+        if !fits {
+            // CNT_ECAP left the counts; any other status comes back from the second call and panics in check
+            rec_cap = counts[1] as usize;
+            rec_text = Vec::with_capacity(rec_cap);
+            rec_start = Vec::with_capacity(rec_cap);
+            check(cnt_fasta_to_bits(text.as_ptr(), len, flags, out.as_mut_ptr(), len, rec_text.as_mut_ptr(), rec_start.as_mut_ptr(), rec_cap, &mut counts));
+        }
+        rec_text.set_len(counts[1] as usize);
+        rec_start.set_len(counts[1] as usize);
+    }
+    out.truncate(words_for(counts[0] as usize));
+    (out, counts[0] as usize, rec_text, rec_start, counts[2])
+}
+
 /// The number of windows `window_counts_hip` reports: `(len - window) / step + 1`, or 0 when `len < window` (no partial window).
 pub fn window_counts_n(len: usize, k: u32, window: usize, step: usize) -> usize {
     let mut n: usize = 0;
@@ -1029,6 +1064,31 @@ pub fn hpc_hip_dev(d_bits: &DeviceBuffer, len: usize, d_out: &DeviceBuffer, d_po
         None => std::ptr::null_mut(),
     };
     unsafe { check(cnt_hpc_dev(d_bits.ptr, len, 0, d_out.ptr, pos_ptr, out_cap, d_count.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `fasta_to_bits_hip_dev` needs for a text of `text_len` bytes (0 when there is none).
+pub fn fasta_to_bits_work_bytes(text_len: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_fasta_to_bits_work_bytes(text_len, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the FASTA encode of `text_len` device-resident bytes (see `fasta_to_bits_hip`): `d_counts` (three u64) is SET to `n`,
+/// the number of header lines and the invalid count.  `d_out` holds at least `words_for(min(text_len, out_cap))` words, the
+/// record arrays (both or neither) at least `min(text_len, rec_cap)` entries, `d_work` at least `fasta_to_bits_work_bytes` bytes.
+pub fn fasta_to_bits_hip_dev(d_text: &DeviceBuffer, text_len: usize, flags: u32, d_out: &DeviceBuffer, out_cap: usize, d_rec: Option<(&DeviceBuffer, &DeviceBuffer)>, rec_cap: usize, d_counts: &DeviceBuffer, d_work: &DeviceBuffer) {
+    assert!(text_len <= d_text.bytes && d_counts.bytes >= 24, "fasta_to_bits_hip_dev: sizes");
+    let most = std::cmp::min(text_len, out_cap);
+    let rmost = std::cmp::min(text_len, rec_cap);
+    assert!(d_out.bytes / 8 >= words_for(most), "fasta_to_bits_hip_dev: out is smaller than its footprint");
+    let (rt, rs) = match d_rec {
+        Some((t, s)) => {
+            assert!(t.bytes / 8 >= rmost && s.bytes / 8 >= rmost, "fasta_to_bits_hip_dev: a record array is smaller than its footprint");
+            (t.ptr, s.ptr)
+        }
+        None => (std::ptr::null_mut(), std::ptr::null_mut()),
+    };
+    unsafe { check(cnt_fasta_to_bits_dev(d_text.ptr, text_len, flags, d_out.ptr, out_cap, rt, rs, rec_cap, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Enqueue the windowed counts of `len` device-resident nucleotides (see `window_counts_hip`): the `window_counts_n` records of
