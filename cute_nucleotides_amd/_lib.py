@@ -144,6 +144,9 @@ SIGNATURES = {
     "cnt_fasta_to_bits_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
     "cnt_fasta_to_bits_dev": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
     "cnt_fasta_to_bits": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_fastq_to_bits_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
+    "cnt_fastq_to_bits_dev": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "cnt_fastq_to_bits": (_int, [_vp, _sz, _uint, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

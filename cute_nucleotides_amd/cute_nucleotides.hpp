@@ -397,6 +397,57 @@ inline Fasta fasta_to_bits_hip(const uint8_t* text, size_t text_len, bool strict
     return r;
 }
 
+/// What packed::fastq_to_bits_hip returns: the n nucleotides packed like any sequence in `out`, the quality bytes in `qual` (empty
+/// without with_qual), one entry per record in `rec_text` (the byte offset of its name line), `rec_start` (the position in `out`
+/// of its first base) and `rec_qual` (the position in `qual` of its first quality; record r ends where record r + 1 starts, the
+/// last one at n and at n_qual), the number of sequence bytes outside the alphabet, and the number of name lines without '@' plus
+/// separator lines without '+'.  A well-formed file has malformed == 0 and rec_qual == rec_start.
+struct Fastq {
+    Vec<uint64_t> out;
+    size_t n = 0;
+    Vec<uint8_t> qual;
+    size_t n_qual = 0;
+    Vec<uint64_t> rec_text, rec_start, rec_qual;
+    uint64_t invalid = 0, malformed = 0;
+};
+
+/// Encode strict four-line FASTQ text (include/cute_nt.h "text formats: FASTQ"): a byte's role is its line number mod 4, line feeds
+/// and carriage returns are dropped, the sequence bytes are encoded as n_to_bits_hip encodes them (`strict_lut`: BYTE_LUT) and the
+/// quality bytes are copied as they are; `allow_n` takes N / n out of the invalid count.  The record arrays start at a guess and
+/// are sized to the reported number of records once if the guess was short.
+inline Fastq fastq_to_bits_hip(const uint8_t* text, size_t text_len, bool strict_lut = false, bool allow_n = false, bool with_qual = true) {
+    const unsigned flags = (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u);
+    size_t rec_cap = text_len < 1024 ? text_len : text_len / 256 + 1024;
+    Fastq r;
+    uint64_t counts[5] = {0, 0, 0, 0, 0};
+    r.out.resize(cnt_words_for(text_len));
+    if (with_qual) r.qual.resize(text_len);
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        r.rec_text.resize(rec_cap);
+        r.rec_start.resize(rec_cap);
+        r.rec_qual.resize(rec_cap);
+        const int rc = cnt_fastq_to_bits(text, text_len, flags, r.out.data(), text_len, with_qual && text_len ? r.qual.data() : nullptr, text_len,
+                                         rec_cap ? r.rec_text.data() : nullptr, rec_cap ? r.rec_start.data() : nullptr, rec_cap ? r.rec_qual.data() : nullptr,
+                                         rec_cap, counts);
+        if (rc == CNT_ECAP && attempt == 0) {
+            rec_cap = counts[CNT_FASTQ_RECORDS];
+            continue;
+        }
+        detail::check(rc);
+        break;
+    }
+    r.n = counts[CNT_FASTQ_N];
+    r.n_qual = with_qual ? counts[CNT_FASTQ_QUAL] : 0;
+    r.invalid = counts[CNT_FASTQ_INVALID];
+    r.malformed = counts[CNT_FASTQ_MALFORMED];
+    r.out.resize(cnt_words_for(r.n));
+    r.qual.resize(r.n_qual);
+    r.rec_text.resize(counts[CNT_FASTQ_RECORDS]);
+    r.rec_start.resize(counts[CNT_FASTQ_RECORDS]);
+    r.rec_qual.resize(counts[CNT_FASTQ_RECORDS]);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -502,6 +553,28 @@ inline void fasta_to_bits_hip_dev(const DeviceBuffer& text, size_t text_len, Dev
     detail::check(cnt_fasta_to_bits_dev(text.data(), text_len, (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u), out.data(), out_cap,
                                         rec_text ? rec_text->data() : nullptr, rec_start ? rec_start->data() : nullptr, rec_cap, counts.data(), work.data(),
                                         work.size_bytes(), nullptr));
+}
+inline size_t fastq_to_bits_work_bytes(size_t text_len) {
+    size_t bytes = 0;
+    detail::check(cnt_fastq_to_bits_work_bytes(text_len, &bytes));
+    return bytes;
+}
+/// Enqueue the FASTQ encode of `text_len` resident bytes (see packed::fastq_to_bits_hip): `counts` (five u64) is SET to n, the
+/// number of records, the invalid count, the number of quality bytes and the malformed count; `out` receives the first
+/// min(n, out_cap) nucleotides and holds at least cnt_words_for(min(text_len, out_cap)) words; `qual` (optional) holds at least
+/// min(text_len, qual_cap) bytes; `rec_text`, `rec_start` and `rec_qual` (all three or none) hold at least min(text_len, rec_cap)
+/// entries; `work` >= fastq_to_bits_work_bytes(text_len) bytes of any contents.
+inline void fastq_to_bits_hip_dev(const DeviceBuffer& text, size_t text_len, DeviceBuffer& out, size_t out_cap, DeviceBuffer* qual, size_t qual_cap,
+                                  DeviceBuffer* rec_text, DeviceBuffer* rec_start, DeviceBuffer* rec_qual, size_t rec_cap, DeviceBuffer& counts, DeviceBuffer& work,
+                                  bool strict_lut = false, bool allow_n = false) {
+    if (text_len > text.size_bytes() || counts.size_bytes() < 40) throw std::out_of_range("fastq_to_bits_hip_dev: sizes");
+    const size_t most = text_len < out_cap ? text_len : out_cap, qmost = text_len < qual_cap ? text_len : qual_cap, rmost = text_len < rec_cap ? text_len : rec_cap;
+    if (out.size_bytes() / 8 < cnt_words_for(most) || (qual && qual->size_bytes() < qmost) || (rec_text && rec_text->size_bytes() / 8 < rmost) ||
+        (rec_start && rec_start->size_bytes() / 8 < rmost) || (rec_qual && rec_qual->size_bytes() / 8 < rmost))
+        throw std::out_of_range("fastq_to_bits_hip_dev: an output is smaller than its footprint");
+    detail::check(cnt_fastq_to_bits_dev(text.data(), text_len, (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u), out.data(), out_cap,
+                                        qual ? qual->data() : nullptr, qual_cap, rec_text ? rec_text->data() : nullptr, rec_start ? rec_start->data() : nullptr,
+                                        rec_qual ? rec_qual->data() : nullptr, rec_cap, counts.data(), work.data(), work.size_bytes(), nullptr));
 }
 /// Enqueue the windowed counts of `len` resident nucleotides (see packed::window_counts_hip): the packed::window_counts_n records
 /// of 4^k u32 in `out` are SET, nothing behind them is written.  No scratch.

@@ -4,10 +4,11 @@ complement, reverse complement, k-mer extraction (forward and canonical), k-mer 
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
 frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, base and dinucleotide
 counts per window (GC content on top of them), alphabet validation of ASCII buffers, and the encode of FASTA text with its
-record table.  The reference does
+record table and of FASTQ text with its qualities and record table.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
+import collections
 import ctypes
 
 import numpy as np
@@ -500,6 +501,60 @@ def fasta_names(text, rec_text):
     return names
 
 
+Fastq = collections.namedtuple("Fastq", "words n qual rec_text rec_start rec_qual invalid malformed")
+
+
+def fastq_to_bits_hip(text, strict_lut=False, allow_n=False, with_qual=True):
+    """Encode strict four-line FASTQ text (include/cute_nt.h "text formats: FASTQ"): the role of a byte is its line number mod 4
+    (name, sequence, separator, quality), line feeds and carriage returns are dropped, the sequence bytes are encoded as
+    n_to_bits_hip encodes them (strict_lut: BYTE_LUT) and the quality bytes are copied as they are.  `text` is bytes, a bytearray,
+    an mmap or a uint8 array.  Returns the named tuple (words, n, qual, rec_text, rec_start, rec_qual, invalid, malformed):
+    np.uint64[words_for(n)] holding the n nucleotides; the quality bytes as np.uint8 (None without with_qual); per record the byte
+    offset of its name line and the positions of its first base in `words` and of its first quality in `qual` (record r ends at
+    entry r + 1, the last one at n and at qual.size; fastq_names gives the names); the number of sequence bytes outside ACGTUacgtu
+    (allow_n: and Nn); and the number of name lines that do not begin with '@' plus separator lines that do not begin with '+'.
+    A well-formed file has malformed == 0 and rec_qual equal to rec_start.  The record arrays start at a guess of the number of
+    records and are sized to the reported number once if the guess was short."""
+    text = _fasta_text(text)
+    length = text.size
+    flags = (_lib.CNT_STRICT_LUT if strict_lut else 0) | (CNT_ALLOW_N if allow_n else 0)
+    out = np.empty(lib().cnt_words_for(length), dtype=np.uint64)
+    qual = np.empty(length, dtype=np.uint8) if with_qual else None
+    rec_cap = min(length, length // 256 + 1024)  # a record every 256 bytes or so
+    counts = (ctypes.c_uint64 * 5)()
+    for attempt in range(2):
+        rec = [np.empty(rec_cap, dtype=np.uint64) for _ in range(3)]
+        rc = lib().cnt_fastq_to_bits(_p(text), length, flags, _p(out) if length else None, length, _p(qual) if with_qual and length else None, length,
+                                     _p(rec[0]), _p(rec[1]), _p(rec[2]), rec_cap, counts)
+        if rc == _lib.CNT_ECAP and attempt == 0:
+            rec_cap = counts[1]
+            continue
+        check(rc)
+        n, records = counts[0], counts[1]
+        return Fastq(out[: lib().cnt_words_for(n)], n, qual[: counts[3]] if with_qual else None, rec[0][:records], rec[1][:records], rec[2][:records],
+                     counts[2], counts[4])
+
+
+def fastq_names(text, rec_text):
+    """the name lines of a FASTQ text at the byte offsets fastq_to_bits_hip reported, as a list of bytes: each without its '@' and
+    without its line end (a line feed, or a carriage return and a line feed; the last line may have neither)"""
+    buf = _fasta_text(text)
+    names = []
+    for at in np.asarray(rec_text, dtype=np.uint64).tolist():
+        if at >= buf.size or buf[at] != 0x40 or (at and buf[at - 1] != 0x0A):
+            raise ValueError("no name line starts at byte %d" % at)
+        line, look = b"", 256
+        while True:  # a look at a time, so that a short name in a long text costs its own length
+            piece = buf[at + 1 + len(line) : at + 1 + len(line) + look].tobytes()
+            end = piece.find(b"\n")
+            line += piece if end < 0 else piece[:end]
+            if end >= 0 or len(piece) < look:
+                break
+            look *= 4
+        names.append(line[:-1] if line.endswith(b"\r") else line)
+    return names
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -831,6 +886,60 @@ def fasta_to_bits_dev(text, out, counts, work, rec_text=None, rec_start=None, ou
              ctypes.c_void_p(rec_text.data_ptr() or spare) if rec_text is not None else None,
              ctypes.c_void_p(rec_start.data_ptr() or spare) if rec_text is not None else None, rec_cap, ctypes.c_void_p(counts.data_ptr()),
              ctypes.c_void_p(work.data_ptr() or spare), work.numel() * work.element_size())
+
+
+def fastq_to_bits_work_bytes(text_len):
+    """bytes of device scratch cnt_fastq_to_bits_dev needs for a text of this many bytes (0 without a byte)"""
+    return _work_bytes(lib().cnt_fastq_to_bits_work_bytes, text_len)
+
+
+def fastq_to_bits_dev(text, out, counts, work, qual=None, rec_text=None, rec_start=None, rec_qual=None, out_cap=None, qual_cap=None, rec_cap=None,
+                      strict_lut=False, allow_n=False):
+    """Device tier of fastq_to_bits_hip, enqueued on torch's current stream without a synchronisation; returns nothing.  All
+    tensors are the caller's, contiguous and on the text's device: `text` (uint8, at any byte address) the FASTQ bytes, `out`
+    (int64) receives the nucleotides packed, `qual` (uint8, at any byte address, optional) the quality bytes, `rec_text`,
+    `rec_start` and `rec_qual` (int64, all three or none) the record table, `counts` (int64, five elements) is SET to n, the number
+    of records, the invalid count, the number of quality bytes and the malformed count, `work` holds >=
+    fastq_to_bits_work_bytes(text.numel()) bytes of any contents.  `out_cap` (nucleotides), `qual_cap` (bytes) and `rec_cap`
+    (records) default to what the outputs can hold and bound what is written.  Every tensor may be reused across calls, e.g. in a
+    captured graph."""
+    torch = _dev_guard(text)
+    if text.dtype != torch.uint8:
+        raise TypeError("text must be a uint8 tensor")
+    recs = (rec_text, rec_start, rec_qual)
+    if any(r is None for r in recs) != all(r is None for r in recs):
+        raise ValueError("rec_text, rec_start and rec_qual go together")
+    for name, t, dtype in (("out", out, torch.int64), ("qual", qual, torch.uint8), ("rec_text", rec_text, torch.int64), ("rec_start", rec_start, torch.int64),
+                           ("rec_qual", rec_qual, torch.int64), ("counts", counts, torch.int64), ("work", work, None)):
+        if t is None and (name.startswith("rec_") or name == "qual"):
+            continue
+        if not hasattr(t, "is_cuda") or (dtype is not None and t.dtype != dtype):
+            raise TypeError("%s must be a%s tensor" % (name, (" uint8" if dtype == torch.uint8 else "n int64") if dtype is not None else ""))
+        if not t.is_cuda or not t.is_contiguous() or t.device != text.device:
+            raise ValueError("%s must be a contiguous CUDA tensor on the text's device" % name)
+    if counts.numel() < 5:
+        raise ValueError("counts must hold five elements")
+    length = text.numel()
+    need = fastq_to_bits_work_bytes(length)
+    if work.numel() * work.element_size() < need:
+        raise ValueError("work must hold >= %d bytes" % need)
+    fits = min(length, out.numel() * 32)
+    out_cap = fits if out_cap is None else int(out_cap)
+    if out_cap < 0 or min(length, out_cap) > fits:
+        raise ValueError("out_cap nucleotides do not fit out")
+    qual_fits = min(length, qual.numel()) if qual is not None else 0
+    qual_cap = qual_fits if qual_cap is None else int(qual_cap)
+    if qual_cap < 0 or (qual is not None and min(length, qual_cap) > qual_fits):
+        raise ValueError("qual_cap bytes do not fit qual")
+    rec_fits = min(length, *(r.numel() for r in recs)) if rec_text is not None else 0
+    rec_cap = rec_fits if rec_cap is None else int(rec_cap)
+    if rec_cap < 0 or (rec_text is not None and min(length, rec_cap) > rec_fits):
+        raise ValueError("rec_cap records do not fit the record arrays")
+    spare = counts.data_ptr()  # an empty tensor has no address (data_ptr() 0); at capacity 0 nothing is written, any aligned address will do
+    flags = (_lib.CNT_STRICT_LUT if strict_lut else 0) | (CNT_ALLOW_N if allow_n else 0)
+    at = lambda t: ctypes.c_void_p(t.data_ptr() or spare) if t is not None else None  # noqa: E731
+    _enqueue(text, lib().cnt_fastq_to_bits_dev, ctypes.c_void_p(text.data_ptr()), length, flags, at(out), out_cap, at(qual), qual_cap, at(rec_text), at(rec_start),
+             at(rec_qual), rec_cap, ctypes.c_void_p(counts.data_ptr()), at(work), work.numel() * work.element_size())
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -814,7 +814,7 @@ int cnt_window_counts(const uint64_t *bits, size_t len, unsigned k, size_t windo
  *   memory: a lane spends about 50 VALU operations per dword on its byte masks; no counters were collected.
  * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
  *   n > out_cap or R > rec_cap the clipped results are written and the call returns CNT_ECAP after the work, as cnt_hpc does.
- * Out of scope: FASTQ, multi-line ';' comments, a 5-letter variant, a nucleotide-to-byte-offset map, line-wrapped decode, gzip. */
+ * Out of scope: FASTQ (the next section), multi-line ';' comments, a 5-letter variant, a nucleotide-to-byte-offset map, line-wrapped decode, gzip. */
 #define CNT_FASTA_N 0        /* counts[0]: nucleotides kept            */
 #define CNT_FASTA_RECORDS 1  /* counts[1]: header lines                */
 #define CNT_FASTA_INVALID 2  /* counts[2]: kept bytes cnt_validate would count */
@@ -824,6 +824,83 @@ int cnt_fasta_to_bits_dev(const void *d_text, size_t text_len, unsigned flags, v
                           size_t work_bytes, void *stream);
 int cnt_fasta_to_bits(const uint8_t *text, size_t text_len, unsigned flags, uint64_t *out, size_t out_cap,
                       uint64_t *rec_text, uint64_t *rec_start, size_t rec_cap, uint64_t counts[3]);
+
+/* ---- text formats: FASTQ ---------------------------------------------------------- */
+/* FASTQ text straight to packed words, with the quality bytes and a record table: what reads need instead of a strip of names,
+ * '+' lines and qualities on the CPU in front of the encoder.  For the bytes t_0 .. t_{L-1} of `text`, L = text_len, and nothing
+ * outside them:
+ *   line start    p is one iff p < L and (p == 0 or t_{p-1} == 0x0A); the byte in front of `text` is never read, and a final
+ *                 line feed opens no line
+ *   line number   of byte p: k(p) = #{ q < p : t_q == 0x0A }; a line feed belongs to the line it ends
+ *   role          of byte p: k(p) mod 4 -- 0 the name line, 1 the sequence, 2 the separator, 3 the quality.  This is strict
+ *                 four-line FASTQ: nothing is inferred from '@' or '+' inside lines, since a quality line may begin with either
+ *   dropped       every 0x0A and every 0x0D, in every role
+ *   sequence      the bytes of role 1 that are not dropped, at q_0 < .. < q_{n-1}.  out is exactly what cnt_n_to_bits_ex(those
+ *                 bytes, n, out, ., flags & CNT_STRICT_LUT) writes.  out_cap is in NUCLEOTIDES; footprint, clipping and the
+ *                 zeroed slots of the last word follow cnt_fasta_to_bits: cnt_words_for(min(text_len, out_cap)) words
+ *   quality       the bytes of role 3 that are not dropped, at u_0 < .. < u_{Q-1}, copied unchanged and in order to `qual`.
+ *                 qual is optional (NULL: not wanted) and may sit at any byte address.  qual_cap is in BYTES: the first
+ *                 min(Q, qual_cap) bytes are written.  The footprint is min(text_len, qual_cap) bytes, unspecified contents
+ *                 behind the result, nothing outside it touched
+ *   records       the line starts of role 0 are h_0 < .. < h_{R-1}: rec_text[r] = h_r, rec_start[r] = #{ j : q_j < h_r } and
+ *                 rec_qual[r] = #{ j : u_j < h_r }.  Give all three arrays or none.  Entries r < min(R, rec_cap) are written
+ *                 and nothing past them.  Record r holds the bases [rec_start[r], rec_start[r+1]) and the qualities
+ *                 [rec_qual[r], rec_qual[r+1]); the last record ends at n and at Q.  A well-formed file has rec_qual ==
+ *                 rec_start and Q == n; the call does not enforce this, it gives both arrays so that one comparison decides it
+ *   counts        five u64 the call SETS, whether or not the results fitted: counts[CNT_FASTQ_N] = n, counts[CNT_FASTQ_RECORDS]
+ *                 = R, counts[CNT_FASTQ_INVALID] = the sequence bytes that cnt_validate with flags & CNT_ALLOW_N counts,
+ *                 counts[CNT_FASTQ_QUAL] = Q, counts[CNT_FASTQ_MALFORMED] = the role-0 line starts whose byte is not '@' plus
+ *                 the role-2 line starts whose byte is not '+' (a blank line in either place counts)
+ *   flags         any of CNT_STRICT_LUT | CNT_ALLOW_N; every other bit is refused
+ * Checks, all before any device work, in this order:
+ *   1. an unknown flag, or, for the query, a NULL bytes: CNT_EINVAL.
+ *   2. text_len == 0: CNT_OK, counts set to zeros when it is given (40 bytes; the device tier by a memset on the stream),
+ *      nothing else touched.
+ *   3. a NULL text, out or counts: CNT_EINVAL.
+ *   4. an out, counts, rec_text, rec_start or rec_qual that is not 8-B aligned: CNT_EINVAL.  text and qual may be at ANY byte.
+ *   5. some but not all of the three record arrays: CNT_EINVAL.
+ *   6. a written buffer sharing a byte with another buffer of the call: CNT_EINVAL.  The extents are text_len bytes, the
+ *      footprint of out, min(text_len, qual_cap) bytes of qual, min(text_len, rec_cap) entries of each record array and 40
+ *      bytes of counts.
+ *   7. device tier: a NULL d_work, work_bytes below the query's answer, or the query's bytes of d_work overlapping anything
+ *      else: CNT_EINVAL.
+ * text_len goes up to 2^36.
+ * Device tier: enqueue-only on the caller's stream: no allocation, no synchronisation, capturable in a graph; d_work is caller
+ *   scratch that nobody needs zeroed, and its size depends on no address.  No byte outside [d_text, d_text + text_len) is read;
+ *   nothing outside the footprints, the clipped record arrays and the counts is written.  Six passes over FASTA's tiles of 8192
+ *   bytes, 256 lanes of 32 bytes (hip/fastq_kernels.hpp): a line count per tile; ONE workgroup that carries the line number mod 4
+ *   from tile to tile -- through tiles without any line feed; a count pass (per tile: its sequence bytes, quality bytes, records,
+ *   invalid bytes and malformed line starts); ONE workgroup that scans the three streams (no atomic); cnt_hpc's edge zeroing;
+ *   and a write pass that encodes and compresses a lane's sequence bytes as cnt_fasta_to_bits does, stages the tile's quality
+ *   bytes in LDS at the 16-B phase of their destination and stores them in aligned 16-B pieces, and lets the lanes that hold
+ *   records store their three table entries.
+ *   Measured on one MI355X, 2026-10-20, product build (DESIGN.md 4 "FASTQ encode", profiles/fastq_bench.jsonl): 2^30 bytes of four-line
+ *   records with 40-byte names take 1.555 ms with reads of 150 bases and line feeds, 1.567 ms with carriage return + line feed and
+ *   1.440 ms with reads of 20,000 bases (691 / 685 / 746 GB/s of text; cnt_fasta_to_bits: 1032 GB/s), and 1.174 / 1.174 / 1.051 ms
+ *   without qual and the record arrays.  In the same run cnt_n_to_bits_checked_dev on the already-stripped bases plus a device copy
+ *   of the Q quality bytes takes 0.271 / 0.271 / 0.312 ms (the call costs 5.7 x / 5.8 x / 4.6 x that floor), and a torch
+ *   boolean-mask strip with both masks given -- text[seq_mask] through cnt_n_to_bits_dev, and text[qual_mask] -- 13.61 / 13.53 /
+ *   14.13 ms (8.8 x / 8.6 x / 9.8 x the call).  rocprofv3 --kernel-trace --stats (profiles/fastq_kernel_trace.md) splits a call on
+ *   reads of 150 into fastq_lines 185 us, fastq_line_scan 22 us, fastq_count 418 us, fastq_scan 184 us, hpc_zero_edges 7 us,
+ *   fastq_write_qual_rec 802 us (652 us on reads of 20,000).  The tile passes are not bound by memory; VALU work on the byte masks,
+ *   and the byte-wise LDS staging of the lanes that hold a line end, is the supposed bound: no counters were collected.
+ * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
+ *   n > out_cap, when qual is given and Q > qual_cap, or when the record arrays are given and R > rec_cap, the clipped results
+ *   are written and the call returns CNT_ECAP after the work.
+ * Out of scope: sequences or qualities wrapped over several lines, a 5-letter variant, quality binning or Phred decoding, paired
+ * or interleaved files, gzip. */
+#define CNT_FASTQ_N 0          /* counts[0]: nucleotides                  */
+#define CNT_FASTQ_RECORDS 1    /* counts[1]: records (role-0 line starts) */
+#define CNT_FASTQ_INVALID 2    /* counts[2]: sequence bytes cnt_validate would count */
+#define CNT_FASTQ_QUAL 3       /* counts[3]: quality bytes                */
+#define CNT_FASTQ_MALFORMED 4  /* counts[4]: name lines without '@', separators without '+' */
+int cnt_fastq_to_bits_work_bytes(size_t text_len, size_t *bytes);
+int cnt_fastq_to_bits_dev(const void *d_text, size_t text_len, unsigned flags, void *d_out, size_t out_cap, void *d_qual,
+                          size_t qual_cap, void *d_rec_text, void *d_rec_start, void *d_rec_qual, size_t rec_cap,
+                          void *d_counts, void *d_work, size_t work_bytes, void *stream);
+int cnt_fastq_to_bits(const uint8_t *text, size_t text_len, unsigned flags, uint64_t *out, size_t out_cap, uint8_t *qual,
+                      size_t qual_cap, uint64_t *rec_text, uint64_t *rec_start, uint64_t *rec_qual, size_t rec_cap,
+                      uint64_t counts[5]);
 
 /* Kernel selection for A/B runs: LAB BUILD ONLY.  The product library (libcute_nt_hip.so) holds the shipped default of every
  * kernel family plus the any-alignment kernels and has NO run-time selection of code: cnt_set_tuning answers CNT_EINVAL for

@@ -92,6 +92,9 @@ extern "C" {
     fn cnt_fasta_to_bits_work_bytes(text_len: usize, bytes: *mut usize) -> c_int;
     fn cnt_fasta_to_bits_dev(d_text: *const c_void, text_len: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, d_rec_text: *mut c_void, d_rec_start: *mut c_void, rec_cap: usize, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_fasta_to_bits(text: *const u8, text_len: usize, flags: c_uint, out: *mut u64, out_cap: usize, rec_text: *mut u64, rec_start: *mut u64, rec_cap: usize, counts: &mut [u64; 3]) -> c_int; // uint64_t counts[3]: a reference to three u64 is that pointer
+    fn cnt_fastq_to_bits_work_bytes(text_len: usize, bytes: *mut usize) -> c_int;
+    fn cnt_fastq_to_bits_dev(d_text: *const c_void, text_len: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, d_qual: *mut c_void, qual_cap: usize, d_rec_text: *mut c_void, d_rec_start: *mut c_void, d_rec_qual: *mut c_void, rec_cap: usize, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_fastq_to_bits(text: *const u8, text_len: usize, flags: c_uint, out: *mut u64, out_cap: usize, qual: *mut u8, qual_cap: usize, rec_text: *mut u64, rec_start: *mut u64, rec_qual: *mut u64, rec_cap: usize, counts: &mut [u64; 5]) -> c_int; // uint64_t counts[5]
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -780,6 +783,55 @@ pub fn fasta_to_bits_hip(text: &[u8], strict_lut: bool, allow_n: bool) -> (Vec<u
     (out, counts[0] as usize, rec_text, rec_start, counts[2])
 }
 
+/// What `fastq_to_bits_hip` returns.  Record `r` holds the bases `[rec_start[r], rec_start[r + 1])` of `out` and the qualities
+/// `[rec_qual[r], rec_qual[r + 1])` of `qual`; the last record ends at `n` and at `qual.len()`.  A well-formed file has
+/// `malformed == 0` and `rec_qual == rec_start`.
+pub struct Fastq {
+    pub out: Vec<u64>,
+    pub n: usize,
+    pub qual: Vec<u8>,
+    pub rec_text: Vec<u64>,
+    pub rec_start: Vec<u64>,
+    pub rec_qual: Vec<u64>,
+    pub invalid: u64,
+    pub malformed: u64,
+}
+
+/// Strict four-line FASTQ text to packed words, quality bytes and a record table: a byte's role is its line number mod 4 (name,
+/// sequence, separator, quality), line feeds and carriage returns are dropped, the sequence bytes are encoded as `n_to_bits_hip`
+/// encodes them (`strict_lut`: the byte table), the quality bytes are copied as they are (`with_qual`).  `invalid` counts the
+/// sequence bytes outside `ACGTUacgtu` (`allow_n`: and `Nn`), `malformed` the name lines without `@` plus the separators without `+`.
+pub fn fastq_to_bits_hip(text: &[u8], strict_lut: bool, allow_n: bool, with_qual: bool) -> Fastq {
+    let len = text.len();
+    let flags: c_uint = (if strict_lut { 1 } else { 0 }) | (if allow_n { 2 } else { 0 });
+    let mut out: Vec<u64> = vec![0u64; words_for(len)];
+    if len == 0 {
+        return Fastq { out, n: 0, qual: Vec::new(), rec_text: Vec::new(), rec_start: Vec::new(), rec_qual: Vec::new(), invalid: 0, malformed: 0 };
+    }
+    let mut qual: Vec<u8> = vec![0u8; if with_qual { len } else { 0 }];
+    let qual_ptr = if with_qual { qual.as_mut_ptr() } else { std::ptr::null_mut() };
+    // a record every 256 bytes or so; a longer table is fetched again at its reported size
+    let mut rec_cap = std::cmp::min(len, len / 256 + 1024);
+    let mut rec: [Vec<u64>; 3] = [Vec::with_capacity(rec_cap), Vec::with_capacity(rec_cap), Vec::with_capacity(rec_cap)];
+    let mut counts = [0u64; 5];
+    unsafe {
+        let fits = cnt_fastq_to_bits(text.as_ptr(), len, flags, out.as_mut_ptr(), len, qual_ptr, len, rec[0].as_mut_ptr(), rec[1].as_mut_ptr(), rec[2].as_mut_ptr(), rec_cap, &mut counts) == 0;
+        if !fits {
+            // CNT_ECAP left the counts; any other status comes back from the second call and panics in check
+            rec_cap = counts[1] as usize;
+            rec = [Vec::with_capacity(rec_cap), Vec::with_capacity(rec_cap), Vec::with_capacity(rec_cap)];
+            check(cnt_fastq_to_bits(text.as_ptr(), len, flags, out.as_mut_ptr(), len, qual_ptr, len, rec[0].as_mut_ptr(), rec[1].as_mut_ptr(), rec[2].as_mut_ptr(), rec_cap, &mut counts));
+        }
+        for r in rec.iter_mut() {
+            r.set_len(counts[1] as usize);
+        }
+    }
+    out.truncate(words_for(counts[0] as usize));
+    qual.truncate(if with_qual { counts[3] as usize } else { 0 });
+    let [rec_text, rec_start, rec_qual] = rec;
+    Fastq { out, n: counts[0] as usize, qual, rec_text, rec_start, rec_qual, invalid: counts[2], malformed: counts[4] }
+}
+
 /// The number of windows `window_counts_hip` reports: `(len - window) / step + 1`, or 0 when `len < window` (no partial window).
 pub fn window_counts_n(len: usize, k: u32, window: usize, step: usize) -> usize {
     let mut n: usize = 0;
@@ -1089,6 +1141,40 @@ pub fn fasta_to_bits_hip_dev(d_text: &DeviceBuffer, text_len: usize, flags: u32,
         None => (std::ptr::null_mut(), std::ptr::null_mut()),
     };
     unsafe { check(cnt_fasta_to_bits_dev(d_text.ptr, text_len, flags, d_out.ptr, out_cap, rt, rs, rec_cap, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `fastq_to_bits_hip_dev` needs for a text of `text_len` bytes (0 when there is none).
+pub fn fastq_to_bits_work_bytes(text_len: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_fastq_to_bits_work_bytes(text_len, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the FASTQ encode of `text_len` device-resident bytes (see `fastq_to_bits_hip`): `d_counts` (five u64) is SET to `n`, the
+/// number of records, the invalid count, the number of quality bytes and the malformed count.  `d_out` holds at least
+/// `words_for(min(text_len, out_cap))` words, `d_qual` (optional) at least `min(text_len, qual_cap)` bytes, the three record
+/// arrays (all or none) at least `min(text_len, rec_cap)` entries, `d_work` at least `fastq_to_bits_work_bytes` bytes.
+pub fn fastq_to_bits_hip_dev(d_text: &DeviceBuffer, text_len: usize, flags: u32, d_out: &DeviceBuffer, out_cap: usize, d_qual: Option<&DeviceBuffer>, qual_cap: usize, d_rec: Option<(&DeviceBuffer, &DeviceBuffer, &DeviceBuffer)>, rec_cap: usize, d_counts: &DeviceBuffer, d_work: &DeviceBuffer) {
+    assert!(text_len <= d_text.bytes && d_counts.bytes >= 40, "fastq_to_bits_hip_dev: sizes");
+    let most = std::cmp::min(text_len, out_cap);
+    let qmost = std::cmp::min(text_len, qual_cap);
+    let rmost = std::cmp::min(text_len, rec_cap);
+    assert!(d_out.bytes / 8 >= words_for(most), "fastq_to_bits_hip_dev: out is smaller than its footprint");
+    let qp = match d_qual {
+        Some(q) => {
+            assert!(q.bytes >= qmost, "fastq_to_bits_hip_dev: qual is smaller than its footprint");
+            q.ptr
+        }
+        None => std::ptr::null_mut(),
+    };
+    let (rt, rs, rq) = match d_rec {
+        Some((t, s, q)) => {
+            assert!(t.bytes / 8 >= rmost && s.bytes / 8 >= rmost && q.bytes / 8 >= rmost, "fastq_to_bits_hip_dev: a record array is smaller than its footprint");
+            (t.ptr, s.ptr, q.ptr)
+        }
+        None => (std::ptr::null_mut(), std::ptr::null_mut(), std::ptr::null_mut()),
+    };
+    unsafe { check(cnt_fastq_to_bits_dev(d_text.ptr, text_len, flags, d_out.ptr, out_cap, qp, qual_cap, rt, rs, rq, rec_cap, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Enqueue the windowed counts of `len` device-resident nucleotides (see `window_counts_hip`): the `window_counts_n` records of
