@@ -448,6 +448,37 @@ inline Fastq fastq_to_bits_hip(const uint8_t* text, size_t text_len, bool strict
     return r;
 }
 
+/// The most bytes of FASTA text packed::bits_to_fasta_hip writes: a pure host function, the footprint of the device tier's text.
+inline size_t bits_to_fasta_bound(size_t len, size_t n_rec, size_t names_len, size_t width) {
+    size_t bytes = 0;
+    detail::check(cnt_bits_to_fasta_bound(len, n_rec, names_len, width, &bytes));
+    return bytes;
+}
+
+/// What packed::bits_to_fasta_hip returns: the text, and per record the byte offset of its '>'.
+struct FastaText {
+    Vec<uint8_t> text;
+    Vec<uint64_t> rec_text;
+};
+
+/// Write packed nucleotides as FASTA text (include/cute_nt.h "text formats: FASTA write"): the bases in front of rec_start[0] as
+/// headerless lines, then per record '>', its name, a line feed and its bases [rec_start[r], rec_start[r + 1]) -- the last record
+/// ends at len -- in lines of `width` letters (0: one line per record).  `names` and `name_off` (n_rec + 1 offsets into names) go
+/// together or are both null: every name is empty then.  Names are copied as they are.  A rec_start or name_off that descends is
+/// an error and writes nothing.  packed::fasta_to_bits_hip reads the text back to bits, len, rec_start and rec_text.
+inline FastaText bits_to_fasta_hip(const uint64_t* bits, size_t len, const uint64_t* rec_start, size_t n_rec, const uint8_t* names, size_t names_len,
+                                   const uint64_t* name_off, size_t width = 60) {
+    const size_t cap = bits_to_fasta_bound(len, n_rec, names_len, width);
+    FastaText r;
+    r.text.resize(cap ? cap : 1);
+    r.rec_text.resize(n_rec);
+    uint64_t counts[2] = {0, 0};
+    detail::check(cnt_bits_to_fasta(bits, len, rec_start, n_rec, names, names_len, name_off, width, 0u, r.text.data(), cap, n_rec ? r.rec_text.data() : nullptr,
+                                    counts));
+    r.text.resize(counts[CNT_FASTA_OUT_TEXT]);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -553,6 +584,28 @@ inline void fasta_to_bits_hip_dev(const DeviceBuffer& text, size_t text_len, Dev
     detail::check(cnt_fasta_to_bits_dev(text.data(), text_len, (strict_lut ? CNT_STRICT_LUT : 0u) | (allow_n ? CNT_ALLOW_N : 0u), out.data(), out_cap,
                                         rec_text ? rec_text->data() : nullptr, rec_start ? rec_start->data() : nullptr, rec_cap, counts.data(), work.data(),
                                         work.size_bytes(), nullptr));
+}
+inline size_t bits_to_fasta_work_bytes(size_t n_rec) {
+    size_t bytes = 0;
+    detail::check(cnt_bits_to_fasta_work_bytes(n_rec, &bytes));
+    return bytes;
+}
+/// Enqueue the FASTA write of `len` resident nucleotides (see packed::bits_to_fasta_hip): `counts` (two u64) is SET to the bytes of
+/// text and the malformed count; `rec_start` (null without a record) holds n_rec entries, `names` and `name_off` (both or neither)
+/// names_len bytes and n_rec + 1 entries, `text` at least min(packed::bits_to_fasta_bound(...), text_cap) bytes, `rec_text`
+/// (optional) n_rec entries, `work` >= bits_to_fasta_work_bytes(n_rec) bytes of any contents.
+inline void bits_to_fasta_hip_dev(const DeviceBuffer& bits, size_t len, const DeviceBuffer* rec_start, size_t n_rec, const DeviceBuffer* names, size_t names_len,
+                                  const DeviceBuffer* name_off, size_t width, DeviceBuffer& text, size_t text_cap, DeviceBuffer* rec_text, DeviceBuffer& counts,
+                                  DeviceBuffer& work) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    if (counts.size_bytes() < 16 || (rec_start && rec_start->size_bytes() / 8 < n_rec) || (names && names->size_bytes() < names_len) ||
+        (name_off && name_off->size_bytes() / 8 < n_rec + 1))
+        throw std::out_of_range("bits_to_fasta_hip_dev: sizes");
+    const size_t bound = packed::bits_to_fasta_bound(len, n_rec, names_len, width), foot = bound < text_cap ? bound : text_cap;
+    if (text.size_bytes() < foot || (rec_text && rec_text->size_bytes() / 8 < n_rec)) throw std::out_of_range("bits_to_fasta_hip_dev: an output is smaller than its footprint");
+    detail::check(cnt_bits_to_fasta_dev(bits.data(), len, rec_start ? rec_start->data() : nullptr, n_rec, names ? names->data() : nullptr, names_len,
+                                        name_off ? name_off->data() : nullptr, width, 0u, text.data(), text_cap, rec_text ? rec_text->data() : nullptr, counts.data(),
+                                        work.data(), work.size_bytes(), nullptr));
 }
 inline size_t fastq_to_bits_work_bytes(size_t text_len) {
     size_t bytes = 0;

@@ -4,7 +4,8 @@ complement, reverse complement, k-mer extraction (forward and canonical), k-mer 
 windows of one length at the positions a search reported, forward or reverse-complemented), codon translation in any of the six
 frames, the open-reading-frame scan on one or both strands, homopolymer compression with run positions, base and dinucleotide
 counts per window (GC content on top of them), alphabet validation of ASCII buffers, and the encode of FASTA text with its
-record table and of FASTQ text with its qualities and record table.  The reference does
+record table and of FASTQ text with its qualities and record table, and the way back: packed words to FASTA text with
+header lines and wrapped lines.  The reference does
 not implement these (its README.md:20-25,45 only points at them); semantics are defined in
 include/cute_nt.h and restated by the oracle.  Host tier: numpy; device tier: torch tensors on
 torch's current stream."""
@@ -555,6 +556,47 @@ def fastq_names(text, rec_text):
     return names
 
 
+def bits_to_fasta_bound(length, n_rec=0, names_len=0, width=60):
+    """the most bytes of FASTA text bits_to_fasta_hip writes for `length` nucleotides in n_rec records whose names hold names_len
+    bytes, at `width` letters a line: a pure host function, the footprint of the device tier's `text`"""
+    return _work_bytes(lib().cnt_bits_to_fasta_bound, length, n_rec, names_len, width)
+
+
+def _fasta_name_table(names, n_rec):
+    """a list of bytes as fasta_names returns it -> (the names back to back as uint8, never empty; n_rec + 1 uint64 offsets)"""
+    names = [bytes(name) for name in names]
+    if len(names) != n_rec:
+        raise ValueError("one name per record")
+    name_off = np.zeros(n_rec + 1, dtype=np.uint64)
+    name_off[1:] = np.cumsum([len(name) for name in names], dtype=np.uint64)
+    joined = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)  # an address even when every name is empty
+    return joined, name_off
+
+
+def bits_to_fasta_hip(bits, length, rec_start=None, names=None, width=60):
+    """Write packed nucleotides as FASTA text (include/cute_nt.h "text formats: FASTA write"): the bases in front of
+    rec_start[0] as headerless lines, then per record '>', its name, a line feed and its bases [rec_start[r], rec_start[r + 1])
+    -- the last record ends at `length` -- in lines of `width` letters (0: one line per record).  `names` is a list of bytes, one
+    per record, as fasta_names returns it; None: every name is empty.  Names are copied as they are.  Returns (text, rec_text):
+    the text as np.uint8 and the byte offset of every record's '>' as np.uint64.  fasta_to_bits_hip(text) gives `bits`, `length`,
+    `rec_start` and `rec_text` back.  A rec_start that descends or passes `length` is an error and writes nothing."""
+    bits = _packed(bits, length)
+    rec_start = np.zeros(0, dtype=np.uint64) if rec_start is None else _u64(rec_start)
+    n_rec = rec_start.size
+    width = int(width)
+    if width < 0:
+        raise ValueError("width must not be negative")
+    joined, name_off = _fasta_name_table(names, n_rec) if names is not None else (None, None)
+    names_len = int(name_off[-1]) if names is not None else 0
+    cap = bits_to_fasta_bound(length, n_rec, names_len, width)
+    text = np.empty(max(cap, 1), dtype=np.uint8)
+    rec_text = np.empty(n_rec, dtype=np.uint64)
+    counts = (ctypes.c_uint64 * 2)()
+    check(lib().cnt_bits_to_fasta(_p(bits) if length else None, length, _p(rec_start), n_rec, _p(joined) if names is not None else None, names_len,
+                                  _p(name_off) if names is not None else None, width, 0, _p(text), cap, _p(rec_text), counts))
+    return text[: counts[0]], rec_text
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -940,6 +982,55 @@ def fastq_to_bits_dev(text, out, counts, work, qual=None, rec_text=None, rec_sta
     at = lambda t: ctypes.c_void_p(t.data_ptr() or spare) if t is not None else None  # noqa: E731
     _enqueue(text, lib().cnt_fastq_to_bits_dev, ctypes.c_void_p(text.data_ptr()), length, flags, at(out), out_cap, at(qual), qual_cap, at(rec_text), at(rec_start),
              at(rec_qual), rec_cap, ctypes.c_void_p(counts.data_ptr()), at(work), work.numel() * work.element_size())
+
+
+def bits_to_fasta_work_bytes(n_rec):
+    """bytes of device scratch cnt_bits_to_fasta_dev needs for this many records: it depends on nothing else"""
+    return _work_bytes(lib().cnt_bits_to_fasta_work_bytes, n_rec)
+
+
+def bits_to_fasta_dev(bits, length, text, counts, work, rec_start=None, names=None, name_off=None, width=60, rec_text=None, text_cap=None):
+    """Device tier of bits_to_fasta_hip, enqueued on torch's current stream without a synchronisation; returns nothing.  All
+    tensors are the caller's, contiguous and on the input's device: `bits` (int64) the packed words, `rec_start` (int64, optional)
+    the first base of every record, `names` (uint8, at any byte address) and `name_off` (int64, one entry more than rec_start; both
+    or neither) the names back to back and where each begins, `text` (uint8, at any byte address) receives the text, `rec_text`
+    (int64, optional, as long as rec_start) the byte offset of every '>', `counts` (int64, two elements) is SET to the bytes of
+    text and the malformed count, `work` holds >= bits_to_fasta_work_bytes(records) bytes of any contents.  `text_cap` (bytes)
+    defaults to what `text` holds and bounds what is written: min(bits_to_fasta_bound(...), text_cap) bytes at the most.  Every
+    tensor may be reused across calls, e.g. in a captured graph."""
+    torch = _packed_dev(bits, length)
+    if (names is None) != (name_off is None):
+        raise ValueError("names and name_off go together")
+    for name, t, dtype in (("rec_start", rec_start, torch.int64), ("names", names, torch.uint8), ("name_off", name_off, torch.int64), ("text", text, torch.uint8),
+                           ("rec_text", rec_text, torch.int64), ("counts", counts, torch.int64), ("work", work, None)):
+        if t is None and name in ("rec_start", "names", "name_off", "rec_text"):
+            continue
+        if not hasattr(t, "is_cuda") or (dtype is not None and t.dtype != dtype):
+            raise TypeError("%s must be a%s tensor" % (name, (" uint8" if dtype == torch.uint8 else "n int64") if dtype is not None else ""))
+        if not t.is_cuda or not t.is_contiguous() or t.device != bits.device:
+            raise ValueError("%s must be a contiguous CUDA tensor on the input's device" % name)
+    if counts.numel() < 2:
+        raise ValueError("counts must hold two elements")
+    n_rec = rec_start.numel() if rec_start is not None else 0
+    if name_off is not None and name_off.numel() != n_rec + 1:
+        raise ValueError("name_off must hold one entry more than rec_start")
+    if rec_text is not None and rec_text.numel() < n_rec:
+        raise ValueError("rec_text must hold one entry per record")
+    need = bits_to_fasta_work_bytes(n_rec)
+    if work.numel() * work.element_size() < need:
+        raise ValueError("work must hold >= %d bytes" % need)
+    names_len = names.numel() if names is not None else 0
+    width = int(width)
+    if width < 0:
+        raise ValueError("width must not be negative")
+    bound = bits_to_fasta_bound(length, n_rec, names_len, width)
+    text_cap = text.numel() if text_cap is None else int(text_cap)
+    if text_cap < 0 or min(bound, text_cap) > text.numel():
+        raise ValueError("text_cap bytes do not fit text")
+    spare = counts.data_ptr()  # an empty tensor has no address (data_ptr() 0); nothing of it is read or written, any aligned address will do
+    at = lambda t: ctypes.c_void_p(t.data_ptr() or spare) if t is not None else None  # noqa: E731
+    _enqueue(bits, lib().cnt_bits_to_fasta_dev, at(bits) if length else None, length, at(rec_start) if n_rec else None, n_rec, at(names), names_len, at(name_off),
+             width, 0, at(text), text_cap, at(rec_text), ctypes.c_void_p(counts.data_ptr()), at(work), work.numel() * work.element_size())
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -814,7 +814,7 @@ int cnt_window_counts(const uint64_t *bits, size_t len, unsigned k, size_t windo
  *   memory: a lane spends about 50 VALU operations per dword on its byte masks; no counters were collected.
  * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
  *   n > out_cap or R > rec_cap the clipped results are written and the call returns CNT_ECAP after the work, as cnt_hpc does.
- * Out of scope: FASTQ (the next section), multi-line ';' comments, a 5-letter variant, a nucleotide-to-byte-offset map, line-wrapped decode, gzip. */
+ * Out of scope: FASTQ (the next section), multi-line ';' comments, a 5-letter variant, a nucleotide-to-byte-offset map, gzip. */
 #define CNT_FASTA_N 0        /* counts[0]: nucleotides kept            */
 #define CNT_FASTA_RECORDS 1  /* counts[1]: header lines                */
 #define CNT_FASTA_INVALID 2  /* counts[2]: kept bytes cnt_validate would count */
@@ -901,6 +901,85 @@ int cnt_fastq_to_bits_dev(const void *d_text, size_t text_len, unsigned flags, v
 int cnt_fastq_to_bits(const uint8_t *text, size_t text_len, unsigned flags, uint64_t *out, size_t out_cap, uint8_t *qual,
                       size_t qual_cap, uint64_t *rec_text, uint64_t *rec_start, uint64_t *rec_qual, size_t rec_cap,
                       uint64_t counts[5]);
+
+/* ---- text formats: FASTA write ---------------------------------------------------- */
+/* Packed words to FASTA text: header lines, a line feed every `width` letters and one behind each record -- what a caller
+ * holding packed records (a genome that came in through cnt_fasta_to_bits, regions cut out by cnt_extract, homopolymer-
+ * compressed reads) needs instead of cnt_bits_to_n followed by a rebuild of the lines on the CPU.
+ *   bits          cnt_words_for(len) packed words; bits beyond len are ignored
+ *   rec_start     R = n_rec entries, the position of each record's first base: s_r = rec_start[r], and s_R = len.  NULL only
+ *                 when R == 0; the call is then a plain line-wrapped decode
+ *   names         optional: `names` holds names_len bytes and name_off R + 1 offsets into them, name r is names[o_r, o_{r+1}).
+ *                 Give both or neither; neither means every name is empty.  Names are copied as bytes and are NOT validated: a
+ *                 0x0A inside a name is the caller's business
+ *   width         W, the letters per line; W == 0: no wrapping, one line per record
+ *   body(a, b)    with l = b - a: the letters "ACTG"[code(a + i)], the decoder's table; a 0x0A behind every W-th letter; a 0x0A
+ *                 behind the last letter when W == 0 or l % W != 0; l == 0 gives no byte at all.  l + ceil(l / W) bytes, and
+ *                 l + (l > 0) for W == 0
+ *   text          body(0, s_0) ++ for r in 0 .. R-1: '>' ++ name_r ++ 0x0A ++ body(s_r, s_{r+1}).  Bases in front of the first
+ *                 record come out as headerless lines: the mirror image of what cnt_fasta_to_bits reports for them.  On well-
+ *                 formed input cnt_fasta_to_bits gives back from this text the words, len, rec_start and rec_text
+ *   rec_text      optional, R entries: the byte offset of record r's '>' in text
+ *   counts        two u64 the call SETS: counts[CNT_FASTA_OUT_TEXT] = |text|; counts[CNT_FASTA_OUT_MALFORMED] =
+ *                 #{r < R : s_r > s_{r+1}} + #{r < R : o_r > o_{r+1}} + (o_R > names_len)
+ *   malformed     A MALFORMED TABLE WRITES NO TEXT: when the malformed count is not 0, counts[CNT_FASTA_OUT_TEXT] = 0, no byte of
+ *                 text or rec_text is written, and the host tier returns CNT_EINVAL after the work.  Whatever the tables hold,
+ *                 nothing is read outside the cnt_words_for(len) words, the R and R + 1 table entries and the names_len name
+ *                 bytes, and nothing is written outside the footprint
+ *   text_cap      in BYTES: the first min(|text|, text_cap) bytes are the result.  The footprint is min(bound, text_cap) bytes,
+ *                 bound = cnt_bits_to_fasta_bound(len, n_rec, names_len, width) = len + (W ? len / W : 0) + (R + 1) + names_len
+ *                 + 2 R, a pure host function; |text| <= bound whatever the device arrays hold.  Contents behind the result
+ *                 are unspecified, nothing outside the footprint is touched: the convention of cnt_hpc and cnt_fasta_to_bits
+ *   flags         must be 0
+ * Checks, all before any device work, in this order:
+ *   1. an unknown flag, or, for the two queries, a NULL bytes: CNT_EINVAL.
+ *   2. len == 0 and n_rec == 0: CNT_OK, counts set to zeros when it is given (16 bytes; the device tier by a memset on the
+ *      stream), nothing else touched.
+ *   3. a NULL bits with len > 0, a NULL text, a NULL counts, a NULL rec_start with n_rec > 0: CNT_EINVAL.
+ *   4. a bits, rec_start, name_off, rec_text or counts that is not 8-B aligned: CNT_EINVAL.  text and names may be at ANY byte.
+ *   5. names without name_off, or name_off without names: CNT_EINVAL.
+ *   6. the bound overflowing size_t (cnt_bits_to_fasta_bound answers the same), or n_rec above 2^48: CNT_EINVAL.
+ *   7. a written buffer sharing a byte with another buffer of the call: CNT_EINVAL.  The extents are the footprint of text,
+ *      n_rec entries of rec_text, 16 bytes of counts, the words of bits, n_rec entries of rec_start, names_len bytes of names and
+ *      n_rec + 1 entries of name_off.
+ *   8. device tier: a NULL d_work, work_bytes below the query's answer, or the query's bytes of d_work overlapping anything
+ *      else: CNT_EINVAL.
+ * len goes up to 2^36.
+ * Device tier: enqueue-only on the caller's stream: no allocation, no synchronisation, capturable in a graph; d_work is caller
+ *   scratch at any contents and any address, and its size depends on n_rec only.  Four passes (hip/fasta_write_kernels.hpp) over
+ *   the R + 1 pieces of the text, the lead and the records: a size pass, one lane per piece, with a 64-bit scan inside the
+ *   workgroup (a record may hold 2^36 bases); ONE workgroup that scans the workgroups' totals and sets the counts (no atomic); a
+ *   pass that leaves every piece's offset in the scratch and stores rec_text; and a write pass tiled over OUTPUT bytes, 16384 to
+ *   a workgroup and 4096 to a wave on the 16-B grid d_text lies in, sized by the footprint.  A wave finds the pieces of its first
+ *   and last byte by a 64-way search; inside one body (a genome) one division by W + 1 serves the wave and each of a lane's four
+ *   16-B chunks goes on in 32 bits: codes from one funnelled pair of words, the decoder's letter table, the line feed spliced in;
+ *   otherwise (reads) a lane searches the wave's pieces and walks 64 bytes through headers, names and record ends.  Aligned 16-B
+ *   stores inside, guarded byte stores at the text's two ends only.
+ *   Measured on one MI355X, 2026-10-20, product build (DESIGN.md 4 "FASTA write", profiles/fasta_write_bench.jsonl): 2^30 bases at
+ *   width 60 with 40-byte names take 0.472 ms as one record (1.09 GB of text, 2314 GB/s), 0.525 ms as 1024 records of 2^20 bases and
+ *   3.947 ms as 7,158,278 reads of 150 (1.40 GB of text, 354 GB/s).  In the same run cnt_bits_to_n_dev at the same len takes 0.190 /
+ *   0.191 / 0.191 ms (the call costs 2.5 x / 2.7 x / 20.7 x that floor), and the torch alternative -- decode, fill the text with
+ *   line feeds, scatter the letters and the header bytes by index, the indices given -- 3.40 / 3.49 / 4.59 ms (7.2 x / 6.6 x / 1.2 x
+ *   the call).  rocprofv3 --kernel-trace --stats (profiles/fasta_write_kernel_trace.md) splits a call into fasta_out_sizes 5 / 5 / 48
+ *   us, fasta_out_scan 5 / 5 / 67 us, fasta_out_offsets 4 / 5 / 29 us, fasta_out_write 452 / 494 / 3762 us.  The one-record write
+ *   pass moves 1.36 GB in 0.45 ms, 2.4 x the decode's time for 1.34 GB: it is not bound by memory.  The supposed bound is the chain
+ *   of dependent loads in front of a wave's first store (the total, the offsets, the tables, the packed words: giving a wave
+ *   4 KiB instead of 1 KiB and sparing it its second search took the 1024-record shape from 0.778 to 0.525 ms) and about 100 VALU
+ *   operations per 16 bytes; for reads it is the byte-by-byte walk, whose
+ *   branches diverge in every wave.  No counters were collected: both are supposed, not isolated.
+ * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
+ *   |text| > text_cap the prefix is written and the call returns CNT_ECAP after the work.
+ * Out of scope: FASTQ writing, lower case or U, CRLF line ends, a 5-letter (N) variant, gzip, per-record widths, validating names. */
+#define CNT_FASTA_OUT_TEXT 0       /* counts[0]: bytes of text                 */
+#define CNT_FASTA_OUT_MALFORMED 1  /* counts[1]: descents of the two tables    */
+int cnt_bits_to_fasta_bound(size_t len, size_t n_rec, size_t names_len, size_t width, size_t *bytes);
+int cnt_bits_to_fasta_work_bytes(size_t n_rec, size_t *bytes);
+int cnt_bits_to_fasta_dev(const void *d_bits, size_t len, const void *d_rec_start, size_t n_rec, const void *d_names,
+                          size_t names_len, const void *d_name_off, size_t width, unsigned flags, void *d_text,
+                          size_t text_cap, void *d_rec_text, void *d_counts, void *d_work, size_t work_bytes, void *stream);
+int cnt_bits_to_fasta(const uint64_t *bits, size_t len, const uint64_t *rec_start, size_t n_rec, const uint8_t *names,
+                      size_t names_len, const uint64_t *name_off, size_t width, unsigned flags, uint8_t *text,
+                      size_t text_cap, uint64_t *rec_text, uint64_t counts[2]);
 
 /* Kernel selection for A/B runs: LAB BUILD ONLY.  The product library (libcute_nt_hip.so) holds the shipped default of every
  * kernel family plus the any-alignment kernels and has NO run-time selection of code: cnt_set_tuning answers CNT_EINVAL for

@@ -95,6 +95,10 @@ extern "C" {
     fn cnt_fastq_to_bits_work_bytes(text_len: usize, bytes: *mut usize) -> c_int;
     fn cnt_fastq_to_bits_dev(d_text: *const c_void, text_len: usize, flags: c_uint, d_out: *mut c_void, out_cap: usize, d_qual: *mut c_void, qual_cap: usize, d_rec_text: *mut c_void, d_rec_start: *mut c_void, d_rec_qual: *mut c_void, rec_cap: usize, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_fastq_to_bits(text: *const u8, text_len: usize, flags: c_uint, out: *mut u64, out_cap: usize, qual: *mut u8, qual_cap: usize, rec_text: *mut u64, rec_start: *mut u64, rec_qual: *mut u64, rec_cap: usize, counts: &mut [u64; 5]) -> c_int; // uint64_t counts[5]
+    fn cnt_bits_to_fasta_bound(len: usize, n_rec: usize, names_len: usize, width: usize, bytes: *mut usize) -> c_int;
+    fn cnt_bits_to_fasta_work_bytes(n_rec: usize, bytes: *mut usize) -> c_int;
+    fn cnt_bits_to_fasta_dev(d_bits: *const c_void, len: usize, d_rec_start: *const c_void, n_rec: usize, d_names: *const c_void, names_len: usize, d_name_off: *const c_void, width: usize, flags: c_uint, d_text: *mut c_void, text_cap: usize, d_rec_text: *mut c_void, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_bits_to_fasta(bits: *const u64, len: usize, rec_start: *const u64, n_rec: usize, names: *const u8, names_len: usize, name_off: *const u64, width: usize, flags: c_uint, text: *mut u8, text_cap: usize, rec_text: *mut u64, counts: &mut [u64; 2]) -> c_int; // uint64_t counts[2]
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -832,6 +836,42 @@ pub fn fastq_to_bits_hip(text: &[u8], strict_lut: bool, allow_n: bool, with_qual
     Fastq { out, n: counts[0] as usize, qual, rec_text, rec_start, rec_qual, invalid: counts[2], malformed: counts[4] }
 }
 
+/// The most bytes of FASTA text `bits_to_fasta_hip` writes for `len` nucleotides in `n_rec` records whose names hold `names_len`
+/// bytes, at `width` letters a line: a pure host function, the footprint of the device tier's text.
+pub fn bits_to_fasta_bound(len: usize, n_rec: usize, names_len: usize, width: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_bits_to_fasta_bound(len, n_rec, names_len, width, &mut bytes)) };
+    bytes
+}
+
+/// Packed words to FASTA text as `(text, rec_text)`: the bases in front of `rec_start[0]` as headerless lines, then per record
+/// `>`, its name, a line feed and its bases `[rec_start[r], rec_start[r + 1])` -- the last record ends at `len` -- in lines of
+/// `width` letters (0: one line per record).  `names` holds one name per record (or is empty: every name is empty) and is copied
+/// as it is.  `rec_text[r]` is the byte offset of record `r`'s `>`.  `fasta_to_bits_hip(&text, ..)` gives `bits`, `len`,
+/// `rec_start` and `rec_text` back.  Panics on a `rec_start` that descends or passes `len`; nothing is written then.
+pub fn bits_to_fasta_hip(bits: &[u64], len: usize, rec_start: &[u64], names: &[&[u8]], width: usize) -> (Vec<u8>, Vec<u64>) {
+    assert!(len <= bits.len() * 32, "The length is greater than the number of nucleotides!");
+    let n_rec = rec_start.len();
+    assert!(names.is_empty() || names.len() == n_rec, "bits_to_fasta_hip: one name per record");
+    let mut name_off: Vec<u64> = Vec::with_capacity(n_rec + 1);
+    let mut joined: Vec<u8> = Vec::new();
+    name_off.push(0);
+    for name in names {
+        joined.extend_from_slice(name);
+        name_off.push(joined.len() as u64);
+    }
+    joined.push(0); // an address even when every name is empty
+    let names_len = joined.len() - 1;
+    let cap = bits_to_fasta_bound(len, n_rec, names_len, width);
+    let mut text: Vec<u8> = vec![0u8; std::cmp::max(cap, 1)];
+    let mut rec_text: Vec<u64> = vec![0u64; n_rec];
+    let mut counts = [0u64; 2];
+    let (np, op) = if names.is_empty() { (std::ptr::null(), std::ptr::null()) } else { (joined.as_ptr(), name_off.as_ptr()) };
+    unsafe { check(cnt_bits_to_fasta(bits.as_ptr(), len, rec_start.as_ptr(), n_rec, np, names_len, op, width, 0, text.as_mut_ptr(), cap, rec_text.as_mut_ptr(), &mut counts)) };
+    text.truncate(counts[0] as usize);
+    (text, rec_text)
+}
+
 /// The number of windows `window_counts_hip` reports: `(len - window) / step + 1`, or 0 when `len < window` (no partial window).
 pub fn window_counts_n(len: usize, k: u32, window: usize, step: usize) -> usize {
     let mut n: usize = 0;
@@ -1141,6 +1181,45 @@ pub fn fasta_to_bits_hip_dev(d_text: &DeviceBuffer, text_len: usize, flags: u32,
         None => (std::ptr::null_mut(), std::ptr::null_mut()),
     };
     unsafe { check(cnt_fasta_to_bits_dev(d_text.ptr, text_len, flags, d_out.ptr, out_cap, rt, rs, rec_cap, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `bits_to_fasta_hip_dev` needs for `n_rec` records: it depends on nothing else.
+pub fn bits_to_fasta_work_bytes(n_rec: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_bits_to_fasta_work_bytes(n_rec, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the FASTA write of `len` device-resident nucleotides (see `bits_to_fasta_hip`): `d_counts` (two u64) is SET to the bytes
+/// of text and the malformed count.  `d_rec_start` holds `n_rec` entries, `d_names` (names and `n_rec + 1` offsets, or none) the
+/// names back to back, `d_text` at least `min(bits_to_fasta_bound(..), text_cap)` bytes, `d_rec_text` (optional) `n_rec` entries,
+/// `d_work` at least `bits_to_fasta_work_bytes(n_rec)` bytes.
+pub fn bits_to_fasta_hip_dev(d_bits: &DeviceBuffer, len: usize, d_rec_start: Option<&DeviceBuffer>, n_rec: usize, d_names: Option<(&DeviceBuffer, usize, &DeviceBuffer)>, width: usize, d_text: &DeviceBuffer, text_cap: usize, d_rec_text: Option<&DeviceBuffer>, d_counts: &DeviceBuffer, d_work: &DeviceBuffer) {
+    assert!(len <= (d_bits.bytes / 8) * 32 && d_counts.bytes >= 16, "bits_to_fasta_hip_dev: sizes");
+    let rs = match d_rec_start {
+        Some(r) => {
+            assert!(r.bytes / 8 >= n_rec, "bits_to_fasta_hip_dev: rec_start is smaller than n_rec entries");
+            r.ptr
+        }
+        None => std::ptr::null_mut(),
+    };
+    let (np, names_len, op) = match d_names {
+        Some((n, names_len, o)) => {
+            assert!(n.bytes >= names_len && o.bytes / 8 >= n_rec + 1, "bits_to_fasta_hip_dev: the name table is smaller than its extents");
+            (n.ptr, names_len, o.ptr)
+        }
+        None => (std::ptr::null_mut(), 0, std::ptr::null_mut()),
+    };
+    let foot = std::cmp::min(bits_to_fasta_bound(len, n_rec, names_len, width), text_cap);
+    assert!(d_text.bytes >= foot, "bits_to_fasta_hip_dev: text is smaller than its footprint");
+    let rt = match d_rec_text {
+        Some(r) => {
+            assert!(r.bytes / 8 >= n_rec, "bits_to_fasta_hip_dev: rec_text is smaller than n_rec entries");
+            r.ptr
+        }
+        None => std::ptr::null_mut(),
+    };
+    unsafe { check(cnt_bits_to_fasta_dev(d_bits.ptr, len, rs, n_rec, np, names_len, op, width, 0, d_text.ptr, text_cap, rt, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Bytes of device scratch `fastq_to_bits_hip_dev` needs for a text of `text_len` bytes (0 when there is none).
