@@ -12,7 +12,7 @@ from .n_to_bits import (bits_to_n_dev, bits_to_n_hip, bits_to_n_hip_into, bits_t
                         round_trip_checked_dev, round_trip_dev)
 from .n_to_bits2 import (bits_to_n2_dev, bits_to_n2_hip, bits_to_n2_hip_into, n_to_bits2_checked_dev, n_to_bits2_dev, n_to_bits2_hip,
                          n_to_bits2_hip_checked, n_to_bits2_hip_into)
-from .packed_ops import (bits_to_fasta_bound, bits_to_fasta_dev, bits_to_fasta_hip, bits_to_fasta_work_bytes, codon_set, fasta_names, fasta_to_bits_dev, fasta_to_bits_hip, fasta_to_bits_work_bytes, fastq_names, fastq_to_bits_dev, fastq_to_bits_hip, fastq_to_bits_work_bytes, gc_content_hip, hpc_dev, hpc_hip, hpc_minimizers_hip, hpc_work_bytes, orfs_dev, orfs_hip, orfs_work_bytes,
+from .packed_ops import (bits_to_fasta_bound, bits_to_fasta_dev, bits_to_fasta_hip, bits_to_fasta_work_bytes, bits_to_fastq_bound, bits_to_fastq_dev, bits_to_fastq_hip, bits_to_fastq_work_bytes, codon_set, fasta_names, fasta_to_bits_dev, fasta_to_bits_hip, fasta_to_bits_work_bytes, fastq_names, fastq_to_bits_dev, fastq_to_bits_hip, fastq_to_bits_work_bytes, gc_content_hip, hpc_dev, hpc_hip, hpc_minimizers_hip, hpc_work_bytes, orfs_dev, orfs_hip, orfs_work_bytes,
                          window_counts_dev, window_counts_hip, window_counts_n)
 
 __all__ = [
@@ -27,4 +27,5 @@ __all__ = [
     "fasta_to_bits_hip", "fasta_to_bits_dev", "fasta_to_bits_work_bytes", "fasta_names",
     "fastq_to_bits_hip", "fastq_to_bits_dev", "fastq_to_bits_work_bytes", "fastq_names",
     "bits_to_fasta_hip", "bits_to_fasta_dev", "bits_to_fasta_work_bytes", "bits_to_fasta_bound",
+    "bits_to_fastq_hip", "bits_to_fastq_dev", "bits_to_fastq_work_bytes", "bits_to_fastq_bound",
 ]

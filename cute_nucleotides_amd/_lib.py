@@ -151,6 +151,10 @@ SIGNATURES = {
     "cnt_bits_to_fasta_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
     "cnt_bits_to_fasta_dev": (_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _uint, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "cnt_bits_to_fasta": (_int, [_vp, _sz, _vp, _sz, _vp, _sz, _vp, _sz, _uint, _vp, _sz, _vp, _vp]),
+    "cnt_bits_to_fastq_bound": (_int, [_sz, _sz, _sz, ctypes.POINTER(_sz)]),
+    "cnt_bits_to_fastq_work_bytes": (_int, [_sz, ctypes.POINTER(_sz)]),
+    "cnt_bits_to_fastq_dev": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _uint, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
+    "cnt_bits_to_fastq": (_int, [_vp, _sz, _vp, _vp, _sz, _vp, _sz, _vp, _uint, _vp, _sz, _vp, _vp]),
     "cnt_set_tuning": (_int, [ctypes.c_char_p, _int]),
     "cnt_get_tuning": (_int, [ctypes.c_char_p, ctypes.POINTER(_int)]),
     "cnt_tuning_name": (ctypes.c_char_p, [ctypes.c_char_p, _int]),

@@ -479,6 +479,32 @@ inline FastaText bits_to_fasta_hip(const uint64_t* bits, size_t len, const uint6
     return r;
 }
 
+/// The most bytes of FASTQ text packed::bits_to_fastq_hip writes: a pure host function, the footprint of the device tier's text.
+inline size_t bits_to_fastq_bound(size_t len, size_t n_rec, size_t names_len) {
+    size_t bytes = 0;
+    detail::check(cnt_bits_to_fastq_bound(len, n_rec, names_len, &bytes));
+    return bytes;
+}
+
+/// Write packed nucleotides and their quality bytes as four-line FASTQ text (include/cute_nt.h "text formats: FASTQ write"): per
+/// record '@', its name, a line feed, its bases [rec_start[r], rec_start[r + 1]) -- the first record begins at 0, the last one ends
+/// at len -- "\n+\n", the quality bytes of the same positions and a line feed.  `qual` holds len bytes; `names` and `name_off`
+/// (n_rec + 1 offsets into names) go together or are both null: every name is empty then.  Names and qualities are copied as they
+/// are.  A table that descends or does not begin at 0 is an error and writes nothing.  Returns the text and per record the byte
+/// offset of its '@'; packed::fastq_to_bits_hip reads the text back.
+inline FastaText bits_to_fastq_hip(const uint64_t* bits, size_t len, const uint8_t* qual, const uint64_t* rec_start, size_t n_rec, const uint8_t* names,
+                                   size_t names_len, const uint64_t* name_off) {
+    const size_t cap = bits_to_fastq_bound(len, n_rec, names_len);
+    FastaText r;
+    r.text.resize(cap ? cap : 1);
+    r.rec_text.resize(n_rec);
+    uint64_t counts[2] = {0, 0};
+    detail::check(cnt_bits_to_fastq(bits, len, qual, rec_start, n_rec, names, names_len, name_off, 0u, r.text.data(), cap, n_rec ? r.rec_text.data() : nullptr,
+                                    counts));
+    r.text.resize(counts[CNT_FASTQ_OUT_TEXT]);
+    return r;
+}
+
 }  // namespace packed
 
 /// Device-resident tier for C++ callers that do not link HIP themselves (the same shape as the Rust binding's
@@ -605,6 +631,28 @@ inline void bits_to_fasta_hip_dev(const DeviceBuffer& bits, size_t len, const De
     if (text.size_bytes() < foot || (rec_text && rec_text->size_bytes() / 8 < n_rec)) throw std::out_of_range("bits_to_fasta_hip_dev: an output is smaller than its footprint");
     detail::check(cnt_bits_to_fasta_dev(bits.data(), len, rec_start ? rec_start->data() : nullptr, n_rec, names ? names->data() : nullptr, names_len,
                                         name_off ? name_off->data() : nullptr, width, 0u, text.data(), text_cap, rec_text ? rec_text->data() : nullptr, counts.data(),
+                                        work.data(), work.size_bytes(), nullptr));
+}
+inline size_t bits_to_fastq_work_bytes(size_t n_rec) {
+    size_t bytes = 0;
+    detail::check(cnt_bits_to_fastq_work_bytes(n_rec, &bytes));
+    return bytes;
+}
+/// Enqueue the FASTQ write of `len` resident nucleotides (see packed::bits_to_fastq_hip): `counts` (two u64) is SET to the bytes of
+/// text and the malformed count; `qual` holds len bytes, `rec_start` n_rec entries, `names` and `name_off` (both or neither)
+/// names_len bytes and n_rec + 1 entries, `text` at least min(packed::bits_to_fastq_bound(...), text_cap) bytes, `rec_text`
+/// (optional) n_rec entries, `work` >= bits_to_fastq_work_bytes(n_rec) bytes of any contents.
+inline void bits_to_fastq_hip_dev(const DeviceBuffer& bits, size_t len, const DeviceBuffer& qual, const DeviceBuffer& rec_start, size_t n_rec,
+                                  const DeviceBuffer* names, size_t names_len, const DeviceBuffer* name_off, DeviceBuffer& text, size_t text_cap,
+                                  DeviceBuffer* rec_text, DeviceBuffer& counts, DeviceBuffer& work) {
+    if (len > ((bits.size_bytes() / 8) << 5)) detail::check(CNT_ELEN);
+    if (counts.size_bytes() < 16 || qual.size_bytes() < len || rec_start.size_bytes() / 8 < n_rec || (names && names->size_bytes() < names_len) ||
+        (name_off && name_off->size_bytes() / 8 < n_rec + 1))
+        throw std::out_of_range("bits_to_fastq_hip_dev: sizes");
+    const size_t bound = packed::bits_to_fastq_bound(len, n_rec, names_len), foot = bound < text_cap ? bound : text_cap;
+    if (text.size_bytes() < foot || (rec_text && rec_text->size_bytes() / 8 < n_rec)) throw std::out_of_range("bits_to_fastq_hip_dev: an output is smaller than its footprint");
+    detail::check(cnt_bits_to_fastq_dev(bits.data(), len, qual.data(), rec_start.data(), n_rec, names ? names->data() : nullptr, names_len,
+                                        name_off ? name_off->data() : nullptr, 0u, text.data(), text_cap, rec_text ? rec_text->data() : nullptr, counts.data(),
                                         work.data(), work.size_bytes(), nullptr));
 }
 inline size_t fastq_to_bits_work_bytes(size_t text_len) {

@@ -597,6 +597,36 @@ def bits_to_fasta_hip(bits, length, rec_start=None, names=None, width=60):
     return text[: counts[0]], rec_text
 
 
+def bits_to_fastq_bound(length, n_rec=0, names_len=0):
+    """the most bytes of FASTQ text bits_to_fastq_hip writes for `length` nucleotides in n_rec records whose names hold names_len
+    bytes: a pure host function, the footprint of the device tier's `text`"""
+    return _work_bytes(lib().cnt_bits_to_fastq_bound, length, n_rec, names_len)
+
+
+def bits_to_fastq_hip(bits, length, qual, rec_start, names=None):
+    """Write packed nucleotides and their quality bytes as four-line FASTQ text (include/cute_nt.h "text formats: FASTQ write"):
+    per record '@', its name, a line feed, its bases [rec_start[r], rec_start[r + 1]) -- the first record begins at 0, the last
+    one ends at `length` -- a line feed, '+', a line feed, the quality bytes of the same positions and a line feed.  `qual` is
+    bytes or a uint8 array of `length` bytes, copied as they are; `names` is a list of bytes, one per record, as fastq_names
+    returns it; None: every name is empty.  Returns the text as bytes; fastq_to_bits_hip(text) gives `bits`, `length`, `qual` and
+    `rec_start` (as rec_start and as rec_qual) back.  A rec_start that descends, passes `length` or does not begin at 0 is an
+    error and writes nothing."""
+    bits = _packed(bits, length)
+    qual = _fasta_text(qual)
+    if qual.size != length:
+        raise ValueError("one quality byte per nucleotide")
+    rec_start = _u64(rec_start)
+    n_rec = rec_start.size
+    joined, name_off = _fasta_name_table(names, n_rec) if names is not None else (None, None)
+    names_len = int(name_off[-1]) if names is not None else 0
+    cap = bits_to_fastq_bound(length, n_rec, names_len)
+    text = np.empty(max(cap, 1), dtype=np.uint8)
+    counts = (ctypes.c_uint64 * 2)()
+    check(lib().cnt_bits_to_fastq(_p(bits) if length else None, length, _p(qual) if length else None, _p(rec_start), n_rec,
+                                  _p(joined) if names is not None else None, names_len, _p(name_off) if names is not None else None, 0, _p(text), cap, None, counts))
+    return text[: counts[0]].tobytes()
+
+
 def validate_hip(n, allow_n=False):
     """Number of bytes that are not nucleotides (0 = the buffer is a valid sequence)."""
     n = _u8(n)
@@ -1031,6 +1061,55 @@ def bits_to_fasta_dev(bits, length, text, counts, work, rec_start=None, names=No
     at = lambda t: ctypes.c_void_p(t.data_ptr() or spare) if t is not None else None  # noqa: E731
     _enqueue(bits, lib().cnt_bits_to_fasta_dev, at(bits) if length else None, length, at(rec_start) if n_rec else None, n_rec, at(names), names_len, at(name_off),
              width, 0, at(text), text_cap, at(rec_text), ctypes.c_void_p(counts.data_ptr()), at(work), work.numel() * work.element_size())
+
+
+def bits_to_fastq_work_bytes(n_rec):
+    """bytes of device scratch cnt_bits_to_fastq_dev needs for this many records: it depends on nothing else"""
+    return _work_bytes(lib().cnt_bits_to_fastq_work_bytes, n_rec)
+
+
+def bits_to_fastq_dev(bits, length, qual, rec_start, text, counts, work, names=None, name_off=None, rec_text=None, text_cap=None):
+    """Device tier of bits_to_fastq_hip, enqueued on torch's current stream without a synchronisation; returns nothing.  All
+    tensors are the caller's, contiguous and on the input's device: `bits` (int64) the packed words, `qual` (uint8, at any byte
+    address, at least `length` bytes) the quality bytes, `rec_start` (int64) the first base of every record, `names` (uint8, at any
+    byte address) and `name_off` (int64, one entry more than rec_start; both or neither) the names back to back and where each
+    begins, `text` (uint8, at any byte address) receives the text, `rec_text` (int64, optional, as long as rec_start) the byte
+    offset of every '@', `counts` (int64, two elements) is SET to the bytes of text and the malformed count, `work` holds >=
+    bits_to_fastq_work_bytes(records) bytes of any contents.  `text_cap` (bytes) defaults to what `text` holds and bounds what is
+    written: min(bits_to_fastq_bound(...), text_cap) bytes at the most.  Every tensor may be reused across calls, e.g. in a
+    captured graph."""
+    torch = _packed_dev(bits, length)
+    if (names is None) != (name_off is None):
+        raise ValueError("names and name_off go together")
+    for name, t, dtype in (("qual", qual, torch.uint8), ("rec_start", rec_start, torch.int64), ("names", names, torch.uint8), ("name_off", name_off, torch.int64),
+                           ("text", text, torch.uint8), ("rec_text", rec_text, torch.int64), ("counts", counts, torch.int64), ("work", work, None)):
+        if t is None and name in ("names", "name_off", "rec_text"):
+            continue
+        if not hasattr(t, "is_cuda") or (dtype is not None and t.dtype != dtype):
+            raise TypeError("%s must be a%s tensor" % (name, (" uint8" if dtype == torch.uint8 else "n int64") if dtype is not None else ""))
+        if not t.is_cuda or not t.is_contiguous() or t.device != bits.device:
+            raise ValueError("%s must be a contiguous CUDA tensor on the input's device" % name)
+    if counts.numel() < 2:
+        raise ValueError("counts must hold two elements")
+    if qual.numel() < length:
+        raise ValueError("qual must hold one byte per nucleotide")
+    n_rec = rec_start.numel()
+    if name_off is not None and name_off.numel() != n_rec + 1:
+        raise ValueError("name_off must hold one entry more than rec_start")
+    if rec_text is not None and rec_text.numel() < n_rec:
+        raise ValueError("rec_text must hold one entry per record")
+    need = bits_to_fastq_work_bytes(n_rec)
+    if work.numel() * work.element_size() < need:
+        raise ValueError("work must hold >= %d bytes" % need)
+    names_len = names.numel() if names is not None else 0
+    bound = bits_to_fastq_bound(length, n_rec, names_len)
+    text_cap = text.numel() if text_cap is None else int(text_cap)
+    if text_cap < 0 or min(bound, text_cap) > text.numel():
+        raise ValueError("text_cap bytes do not fit text")
+    spare = counts.data_ptr()  # an empty tensor has no address (data_ptr() 0); nothing of it is read or written, any aligned address will do
+    at = lambda t: ctypes.c_void_p(t.data_ptr() or spare) if t is not None else None  # noqa: E731
+    _enqueue(bits, lib().cnt_bits_to_fastq_dev, at(bits) if length else None, length, at(qual) if length else None, at(rec_start) if n_rec else None, n_rec,
+             at(names), names_len, at(name_off), 0, at(text), text_cap, at(rec_text), ctypes.c_void_p(counts.data_ptr()), at(work), work.numel() * work.element_size())
 
 
 def validate_dev(n, allow_n=False, acc=None):

@@ -170,7 +170,7 @@ int finish(hipStream_t s, int rc) {
 #include "host_tier.inc"
 #include "sharded_tier.inc"
 
-// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc, window_count_abi.inc, fasta_abi.inc, fastq_abi.inc, fasta_write_abi.inc) --
+// ---- the host tier of the packed-domain operations (packed_ops_abi.inc, kmer_abi.inc, minimizer_abi.inc, find_abi.inc, extract_abi.inc, translate_abi.inc, orf_abi.inc, hpc_abi.inc, window_count_abi.inc, fasta_abi.inc, fastq_abi.inc, fasta_write_abi.inc, fastq_write_abi.inc) --
 // A caller's host buffer.  When the call is staged, `in` is copied to the device before it and `out` back after it; `counted`
 // is copied back in its first *result words only, clipped to the buffer (an output whose length the call reports).
 enum class Dir { in, out, counted };
@@ -910,3 +910,4 @@ const char* cnt_tuning_name(const char* key, int value) {
 #include "fasta_abi.inc"
 #include "fastq_abi.inc"
 #include "fasta_write_abi.inc"
+#include "fastq_write_abi.inc"

@@ -98,26 +98,12 @@ __device__ __forceinline__ FastaOutPiece fasta_out_piece(const FastaOutArgs& a, 
     return q;
 }
 
-// pass 1
-__global__ __launch_bounds__(kFastaOutBlock) void fasta_out_sizes(FastaOutArgs a, uint64_t first_block) {
+// The end of a size pass, shared with the FASTQ writer's (fastq_write_kernels.hpp): piece p of workgroup `block` holds `size`
+// bytes and `bad` descents; the exclusive scan inside the workgroup goes to off[p], the workgroup's two totals to sums[block] and
+// bad[block].  Every thread of the workgroup calls it.
+__device__ __forceinline__ void fasta_out_block_scan(const FastaOutArgs& a, uint64_t block, uint64_t p, uint64_t size, uint64_t bad) {
     __shared__ uint64_t s_sum[kFastaOutWaves], s_bad[kFastaOutWaves];
-    const uint64_t block = first_block + blockIdx.x, p = block * kFastaOutBlock + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint64_t size = 0, bad = 0;
-    if (p == 0) {
-        size = fasta_out_body_bytes(a.n_rec ? a.rec_start[0] : a.len, a.width);
-    } else if (p <= a.n_rec) {
-        const uint64_t r = p - 1;
-        const uint64_t s0 = a.rec_start[r], s1 = r + 1 < a.n_rec ? a.rec_start[r + 1] : a.len;
-        bad = s0 > s1;
-        size = 2 + fasta_out_body_bytes(s0 > s1 ? 0 : s1 - s0, a.width);
-        if (a.name_off) {
-            const uint64_t o0 = a.name_off[r], o1 = a.name_off[r + 1];
-            bad += o0 > o1;
-            if (r + 1 == a.n_rec) bad += o1 > a.names_len;
-            size += o0 > o1 ? 0 : o1 - o0;
-        }
-    }
     uint64_t x = size;  // the inclusive scan over the wave
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -142,6 +128,27 @@ __global__ __launch_bounds__(kFastaOutBlock) void fasta_out_sizes(FastaOutArgs a
         a.sums[block] = total;
         a.bad[block] = bad_total;
     }
+}
+
+// pass 1
+__global__ __launch_bounds__(kFastaOutBlock) void fasta_out_sizes(FastaOutArgs a, uint64_t first_block) {
+    const uint64_t block = first_block + blockIdx.x, p = block * kFastaOutBlock + threadIdx.x;
+    uint64_t size = 0, bad = 0;
+    if (p == 0) {
+        size = fasta_out_body_bytes(a.n_rec ? a.rec_start[0] : a.len, a.width);
+    } else if (p <= a.n_rec) {
+        const uint64_t r = p - 1;
+        const uint64_t s0 = a.rec_start[r], s1 = r + 1 < a.n_rec ? a.rec_start[r + 1] : a.len;
+        bad = s0 > s1;
+        size = 2 + fasta_out_body_bytes(s0 > s1 ? 0 : s1 - s0, a.width);
+        if (a.name_off) {
+            const uint64_t o0 = a.name_off[r], o1 = a.name_off[r + 1];
+            bad += o0 > o1;
+            if (r + 1 == a.n_rec) bad += o1 > a.names_len;
+            size += o0 > o1 ? 0 : o1 - o0;
+        }
+    }
+    fasta_out_block_scan(a, block, p, size, bad);
 }
 
 // pass 2: one workgroup

@@ -981,6 +981,91 @@ int cnt_bits_to_fasta(const uint64_t *bits, size_t len, const uint64_t *rec_star
                       size_t names_len, const uint64_t *name_off, size_t width, unsigned flags, uint8_t *text,
                       size_t text_cap, uint64_t *rec_text, uint64_t counts[2]);
 
+/* ---- text formats: FASTQ write ---------------------------------------------------- */
+/* Packed words and quality bytes to four-line FASTQ text -- what a caller holding reads on the device (they came in through
+ * cnt_fastq_to_bits, were cut by cnt_extract, compressed by cnt_hpc or filtered with cnt_find_pattern) needs instead of
+ * cnt_bits_to_n followed by a rebuild of four lines per read on the CPU.
+ *   bits          cnt_words_for(len) packed words; bits beyond len are ignored
+ *   qual          len bytes at ANY byte address: quality i belongs to base i.  They are copied as bytes and are NOT validated: a
+ *                 0x0A among them is the caller's business.  ONE table serves bases and qualities: a caller coming from
+ *                 cnt_fastq_to_bits first compares its rec_qual with its rec_start
+ *   rec_start     R = n_rec entries, the position of each record's first base: s_r = rec_start[r], and s_R = len
+ *   names         exactly as in cnt_bits_to_fasta: `names` holds names_len bytes and name_off R + 1 offsets into them, name r is
+ *                 names[o_r, o_{r+1}).  Give both or neither; neither means every name is empty.  Names are copied as bytes and
+ *                 are NOT validated
+ *   text          for r in 0 .. R-1: '@' ++ name_r ++ 0x0A ++ the letters "ACTG"[code(i)], the decoder's table, for i in
+ *                 [s_r, s_{r+1}) ++ 0x0A '+' 0x0A ++ qual[s_r, s_{r+1}) ++ 0x0A.  A record is |name_r| + 2 (s_{r+1} - s_r) + 6
+ *                 bytes; an empty record with an empty name is the 6 bytes "@\n\n+\n\n".  No wrapping, no CRLF, no name behind
+ *                 the '+'.  When no name and no quality byte is 0x0A or 0x0D, cnt_fastq_to_bits gives back from this text the
+ *                 words, n = Q = len, qual byte for byte, rec_text as the writer's, rec_start == rec_qual == the input table and
+ *                 no malformed line; names may hold 0x0D, '@' or '+'
+ *   rec_text      optional, R entries: the byte offset of record r's '@' in text
+ *   counts        two u64 the call SETS: counts[CNT_FASTQ_OUT_TEXT] = |text|; counts[CNT_FASTQ_OUT_MALFORMED] =
+ *                 #{r < R : s_r > s_{r+1}} + #{r < R : o_r > o_{r+1}} + (o_R > names_len) + (s_0 != 0).  FASTQ has no
+ *                 headerless lead: bases in front of the first record would belong to nothing, hence the last term
+ *   malformed     A MALFORMED TABLE WRITES NO TEXT: when the malformed count is not 0, counts[CNT_FASTQ_OUT_TEXT] = 0, no byte of
+ *                 text or rec_text is written, and the host tier returns CNT_EINVAL after the work.  Whatever the tables hold,
+ *                 nothing is read outside the cnt_words_for(len) words, the len quality bytes, the R and R + 1 table entries
+ *                 and the names_len name bytes, and nothing is written outside the footprint
+ *   text_cap      in BYTES: the first min(|text|, text_cap) bytes are the result.  The footprint is min(bound, text_cap) bytes,
+ *                 bound = cnt_bits_to_fastq_bound(len, n_rec, names_len) = 2 len + names_len + 6 n_rec, a pure host function;
+ *                 on a well-formed table |text| = 2 len + 6 R + (o_R - o_0) <= bound.  Contents behind the result are
+ *                 unspecified, nothing outside the footprint is touched
+ *   flags         must be 0
+ * Checks, all before any device work, in this order:
+ *   1. an unknown flag, or, for the two queries, a NULL bytes: CNT_EINVAL.
+ *   2. n_rec == 0, whatever len is: CNT_OK, counts set to zeros when it is given (16 bytes; the device tier by a memset on the
+ *      stream), nothing else touched.
+ *   3. a NULL text, a NULL counts, a NULL rec_start, a NULL bits or a NULL qual with len > 0: CNT_EINVAL.
+ *   4. a bits, rec_start, name_off, rec_text or counts that is not 8-B aligned: CNT_EINVAL.  text, qual and names may be at ANY
+ *      byte.
+ *   5. names without name_off, or name_off without names: CNT_EINVAL.
+ *   6. the bound overflowing size_t (cnt_bits_to_fastq_bound answers the same), or n_rec above 2^48: CNT_EINVAL.
+ *   7. a written buffer sharing a byte with another buffer of the call: CNT_EINVAL.  The extents are the footprint of text,
+ *      n_rec entries of rec_text, 16 bytes of counts, the words of bits, len bytes of qual, n_rec entries of rec_start, names_len
+ *      bytes of names and n_rec + 1 entries of name_off.
+ *   8. device tier: a NULL d_work, work_bytes below the query's answer, or the query's bytes of d_work overlapping anything
+ *      else: CNT_EINVAL.
+ * len goes up to 2^36.
+ * Device tier: enqueue-only on the caller's stream: no allocation, no synchronisation, capturable in a graph; d_work is caller
+ *   scratch at any contents and any address, and its size depends on n_rec only.  Four passes (hip/fastq_write_kernels.hpp) over
+ *   the FASTA writer's chain of pieces with an always-empty lead: a size pass of its own, then cnt_bits_to_fasta's scan of the
+ *   workgroups' totals and its offset pass AS THEY ARE (they set the counts and store rec_text), then a write pass of its own,
+ *   tiled over OUTPUT bytes with the FASTA writer's geometry: 16384 bytes to a workgroup, 4096 to a wave, a wave's lanes taking
+ *   its 16-B chunks in turn.  A wave finds the pieces of its first and last byte by a 64-way search, a chunk its own first piece
+ *   by bisection inside that range.  No byte is walked: a chunk loops over the records that overlap it (one, two at a record
+ *   seam, three at the most) and per record lays qualities, '+', letters, name and '@' over a vector of line feeds, each under a
+ *   byte mask from the record's offsets; the letters are one funnelled pair of packed words through the decoder's table, name and
+ *   quality bytes aligned dword loads and v_alignbyte, guarded byte loads only within 20 bytes of a source buffer's two ends.  Aligned
+ *   16-B stores inside, guarded byte stores only at the text's two ends and the text_cap cut.  The chunk is composed in
+ *   registers; no LDS-staged variant was built.
+ *   Measured on one MI355X, 2026-10-20, product build (DESIGN.md 4 "FASTQ write", profiles/fastq_write_bench.jsonl), 2^30 bases and as
+ *   many quality bytes with 40-byte names, every figure from one run in which the four things take turns call by call, as 7,158,278
+ *   reads of 150 (2.48 GB of text) / 53,687 reads of 20,000 (2.15 GB): (a) the call 3.570 / 1.447 ms (694 / 1486 GB/s of text); (b)
+ *   the floor, cnt_bits_to_n_dev at the same len plus device copies of the quality and name bytes, 0.718 / 0.602 ms: a/b = 4.98 /
+ *   2.41; (c) cnt_bits_to_fasta_dev at width 0 on the same table, whose kernel walks bytes at every seam, 3.749 / 0.894 ms for 1.38 /
+ *   1.08 GB of text (369 / 1203 GB/s): a/c = 0.95 / 1.62 in ms, 1.88 / 1.23 in GB/s of text; (d) the torch alternative -- decode,
+ *   fill, scatter letters, qualities, names and constants by index, the indices given -- 8.33 / 6.86 ms (2.3 x / 4.7 x the call).
+ *   rocprofv3 --kernel-trace --stats (profiles/fastq_write_kernel_trace.md) splits a call into fastq_out_sizes 47 / 5 us,
+ *   fasta_out_scan 67 / 5 us, fasta_out_offsets 29 / 5 us, fastq_out_write 3453 / 1429 us.  At five times its floor the write pass
+ *   is not bound by memory; the supposed bound is instruction issue (1355 instructions, most of them in the loop over a chunk's
+ *   records, which a wave runs twice whenever one of its 64 chunks holds a record seam).  No counters were collected: supposed, not
+ *   isolated.
+ * Host tier: synchronous; pinned buffers are used in place, otherwise all of them are staged.  counts is always set; when
+ *   |text| > text_cap the prefix is written and the call returns CNT_ECAP after the work.
+ * Out of scope: wrapped FASTQ lines, CRLF, a name behind the '+', a constant-quality fill, separate rec_qual tables, paired or
+ *   interleaved output, a 5-letter (N) variant, gzip. */
+#define CNT_FASTQ_OUT_TEXT 0       /* counts[0]: bytes of text                          */
+#define CNT_FASTQ_OUT_MALFORMED 1  /* counts[1]: descents of the two tables, s_0 != 0   */
+int cnt_bits_to_fastq_bound(size_t len, size_t n_rec, size_t names_len, size_t *bytes);
+int cnt_bits_to_fastq_work_bytes(size_t n_rec, size_t *bytes);
+int cnt_bits_to_fastq_dev(const void *d_bits, size_t len, const void *d_qual, const void *d_rec_start, size_t n_rec,
+                          const void *d_names, size_t names_len, const void *d_name_off, unsigned flags, void *d_text,
+                          size_t text_cap, void *d_rec_text, void *d_counts, void *d_work, size_t work_bytes, void *stream);
+int cnt_bits_to_fastq(const uint64_t *bits, size_t len, const uint8_t *qual, const uint64_t *rec_start, size_t n_rec,
+                      const uint8_t *names, size_t names_len, const uint64_t *name_off, unsigned flags, uint8_t *text,
+                      size_t text_cap, uint64_t *rec_text, uint64_t counts[2]);
+
 /* Kernel selection for A/B runs: LAB BUILD ONLY.  The product library (libcute_nt_hip.so) holds the shipped default of every
  * kernel family plus the any-alignment kernels and has NO run-time selection of code: cnt_set_tuning answers CNT_EINVAL for
  * every key, the getters answer constants ("encode" = 0, "encode_variants" = 1, "small_nt" = 2^17, "lab_build" = 0, ...) --

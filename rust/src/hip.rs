@@ -99,6 +99,10 @@ extern "C" {
     fn cnt_bits_to_fasta_work_bytes(n_rec: usize, bytes: *mut usize) -> c_int;
     fn cnt_bits_to_fasta_dev(d_bits: *const c_void, len: usize, d_rec_start: *const c_void, n_rec: usize, d_names: *const c_void, names_len: usize, d_name_off: *const c_void, width: usize, flags: c_uint, d_text: *mut c_void, text_cap: usize, d_rec_text: *mut c_void, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
     fn cnt_bits_to_fasta(bits: *const u64, len: usize, rec_start: *const u64, n_rec: usize, names: *const u8, names_len: usize, name_off: *const u64, width: usize, flags: c_uint, text: *mut u8, text_cap: usize, rec_text: *mut u64, counts: &mut [u64; 2]) -> c_int; // uint64_t counts[2]
+    fn cnt_bits_to_fastq_bound(len: usize, n_rec: usize, names_len: usize, bytes: *mut usize) -> c_int;
+    fn cnt_bits_to_fastq_work_bytes(n_rec: usize, bytes: *mut usize) -> c_int;
+    fn cnt_bits_to_fastq_dev(d_bits: *const c_void, len: usize, d_qual: *const c_void, d_rec_start: *const c_void, n_rec: usize, d_names: *const c_void, names_len: usize, d_name_off: *const c_void, flags: c_uint, d_text: *mut c_void, text_cap: usize, d_rec_text: *mut c_void, d_counts: *mut c_void, d_work: *mut c_void, work_bytes: usize, stream: *mut c_void) -> c_int;
+    fn cnt_bits_to_fastq(bits: *const u64, len: usize, qual: *const u8, rec_start: *const u64, n_rec: usize, names: *const u8, names_len: usize, name_off: *const u64, flags: c_uint, text: *mut u8, text_cap: usize, rec_text: *mut u64, counts: &mut [u64; 2]) -> c_int; // uint64_t counts[2]
 }
 
 const CNT_STRICT_LUT: c_uint = 1;
@@ -872,6 +876,44 @@ pub fn bits_to_fasta_hip(bits: &[u64], len: usize, rec_start: &[u64], names: &[&
     (text, rec_text)
 }
 
+/// The most bytes of FASTQ text `bits_to_fastq_hip` writes for `len` nucleotides in `n_rec` records whose names hold `names_len`
+/// bytes: a pure host function, the footprint of the device tier's text.
+pub fn bits_to_fastq_bound(len: usize, n_rec: usize, names_len: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_bits_to_fastq_bound(len, n_rec, names_len, &mut bytes)) };
+    bytes
+}
+
+/// Packed words and quality bytes to four-line FASTQ text as `(text, rec_text)`: per record `@`, its name, a line feed, its bases
+/// `[rec_start[r], rec_start[r + 1])` -- the first record begins at 0, the last one ends at `len` -- a line feed, `+`, a line feed,
+/// the quality bytes of the same positions and a line feed.  `qual` holds `len` bytes; `names` holds one name per record (or is
+/// empty: every name is empty); both are copied as they are.  `rec_text[r]` is the byte offset of record `r`'s `@`.
+/// `fastq_to_bits_hip(&text, ..)` gives `bits`, `len`, `qual` and `rec_start` back.  Panics on a `rec_start` that descends, passes
+/// `len` or does not begin at 0; nothing is written then.
+pub fn bits_to_fastq_hip(bits: &[u64], len: usize, qual: &[u8], rec_start: &[u64], names: &[&[u8]]) -> (Vec<u8>, Vec<u64>) {
+    assert!(len <= bits.len() * 32, "The length is greater than the number of nucleotides!");
+    assert!(qual.len() == len, "bits_to_fastq_hip: one quality byte per nucleotide");
+    let n_rec = rec_start.len();
+    assert!(names.is_empty() || names.len() == n_rec, "bits_to_fastq_hip: one name per record");
+    let mut name_off: Vec<u64> = Vec::with_capacity(n_rec + 1);
+    let mut joined: Vec<u8> = Vec::new();
+    name_off.push(0);
+    for name in names {
+        joined.extend_from_slice(name);
+        name_off.push(joined.len() as u64);
+    }
+    joined.push(0); // an address even when every name is empty
+    let names_len = joined.len() - 1;
+    let cap = bits_to_fastq_bound(len, n_rec, names_len);
+    let mut text: Vec<u8> = vec![0u8; std::cmp::max(cap, 1)];
+    let mut rec_text: Vec<u64> = vec![0u64; n_rec];
+    let mut counts = [0u64; 2];
+    let (np, op) = if names.is_empty() { (std::ptr::null(), std::ptr::null()) } else { (joined.as_ptr(), name_off.as_ptr()) };
+    unsafe { check(cnt_bits_to_fastq(bits.as_ptr(), len, qual.as_ptr(), rec_start.as_ptr(), n_rec, np, names_len, op, 0, text.as_mut_ptr(), cap, rec_text.as_mut_ptr(), &mut counts)) };
+    text.truncate(counts[0] as usize);
+    (text, rec_text)
+}
+
 /// The number of windows `window_counts_hip` reports: `(len - window) / step + 1`, or 0 when `len < window` (no partial window).
 pub fn window_counts_n(len: usize, k: u32, window: usize, step: usize) -> usize {
     let mut n: usize = 0;
@@ -1220,6 +1262,38 @@ pub fn bits_to_fasta_hip_dev(d_bits: &DeviceBuffer, len: usize, d_rec_start: Opt
         None => std::ptr::null_mut(),
     };
     unsafe { check(cnt_bits_to_fasta_dev(d_bits.ptr, len, rs, n_rec, np, names_len, op, width, 0, d_text.ptr, text_cap, rt, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
+}
+
+/// Bytes of device scratch `bits_to_fastq_hip_dev` needs for `n_rec` records: it depends on nothing else.
+pub fn bits_to_fastq_work_bytes(n_rec: usize) -> usize {
+    let mut bytes: usize = 0;
+    unsafe { check(cnt_bits_to_fastq_work_bytes(n_rec, &mut bytes)) };
+    bytes
+}
+
+/// Enqueue the FASTQ write of `len` device-resident nucleotides (see `bits_to_fastq_hip`): `d_counts` (two u64) is SET to the bytes
+/// of text and the malformed count.  `d_qual` holds `len` bytes, `d_rec_start` `n_rec` entries, `d_names` (names and `n_rec + 1`
+/// offsets, or none) the names back to back, `d_text` at least `min(bits_to_fastq_bound(..), text_cap)` bytes, `d_rec_text`
+/// (optional) `n_rec` entries, `d_work` at least `bits_to_fastq_work_bytes(n_rec)` bytes.
+pub fn bits_to_fastq_hip_dev(d_bits: &DeviceBuffer, len: usize, d_qual: &DeviceBuffer, d_rec_start: &DeviceBuffer, n_rec: usize, d_names: Option<(&DeviceBuffer, usize, &DeviceBuffer)>, d_text: &DeviceBuffer, text_cap: usize, d_rec_text: Option<&DeviceBuffer>, d_counts: &DeviceBuffer, d_work: &DeviceBuffer) {
+    assert!(len <= (d_bits.bytes / 8) * 32 && d_qual.bytes >= len && d_rec_start.bytes / 8 >= n_rec && d_counts.bytes >= 16, "bits_to_fastq_hip_dev: sizes");
+    let (np, names_len, op) = match d_names {
+        Some((n, names_len, o)) => {
+            assert!(n.bytes >= names_len && o.bytes / 8 >= n_rec + 1, "bits_to_fastq_hip_dev: the name table is smaller than its extents");
+            (n.ptr, names_len, o.ptr)
+        }
+        None => (std::ptr::null_mut(), 0, std::ptr::null_mut()),
+    };
+    let foot = std::cmp::min(bits_to_fastq_bound(len, n_rec, names_len), text_cap);
+    assert!(d_text.bytes >= foot, "bits_to_fastq_hip_dev: text is smaller than its footprint");
+    let rt = match d_rec_text {
+        Some(r) => {
+            assert!(r.bytes / 8 >= n_rec, "bits_to_fastq_hip_dev: rec_text is smaller than n_rec entries");
+            r.ptr
+        }
+        None => std::ptr::null_mut(),
+    };
+    unsafe { check(cnt_bits_to_fastq_dev(d_bits.ptr, len, d_qual.ptr, d_rec_start.ptr, n_rec, np, names_len, op, 0, d_text.ptr, text_cap, rt, d_counts.ptr, d_work.ptr, d_work.bytes, std::ptr::null_mut())) };
 }
 
 /// Bytes of device scratch `fastq_to_bits_hip_dev` needs for a text of `text_len` bytes (0 when there is none).
